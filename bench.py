@@ -7,9 +7,13 @@ the C ABI (mfa_multihead_forward).  Multi-GPU: one process per GPU, batch x head
 with no collective on the data path; each rank runs its own batch element (weak scaling).
 FLOPs are algorithmic: 4·D per unmasked (query, key) pair.
 
-Also reported (same JSON line): the INT8-K/V path and the fp16 path at configs[2]'s shape
-(H16 S8192 D128, non-causal) and their ratio; the kernel's MFMA roofline fraction measured
-live with HIP events on the launch stream; the CPU oracle timed on a bounded sample.
+A plain run sets up, warms up, times the --steps steps and prints the headline line (with the
+kernel's MFMA roofline fraction from the same HIP-event timing).  --dump-outputs DIR writes
+what the last timed step computed (O, L) as DIR/<name>.npy; the inputs come from a fixed seed.
+
+With --full the same JSON line also carries: the INT8-K/V path and the fp16 path at
+configs[2]'s shape (H16 S8192 D128, non-causal) and their ratio; the C5, MLA, block-sparse,
+SURVEY §8(f) and strong-scaling rows; the CPU oracle timed on a bounded sample.
 """
 from __future__ import annotations
 
@@ -36,6 +40,13 @@ def parse():
     ap.add_argument("--heads", type=int, default=16)
     ap.add_argument("--seq", type=int, default=4096)
     ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side rows (INT8 / INT4, C5 fwd+bwd, MLA, block-sparse, "
+                         "SURVEY §8(f), strong scaling) and the CPU baselines; the --no-* "
+                         "switches below trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (O, L) as "
+                         "DIR/<name>.npy (float32)")
     ap.add_argument("--no-int8", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-c5", action="store_true")
@@ -48,7 +59,11 @@ def parse():
     ap.add_argument("--fake-device", action="store_true",
                     help="CPU dry run of the launch / rank / timing plumbing (gloo, no GPU, "
                          "no kernels); used by the CPU test of the --gpus spawn path")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline only
+        args.no_int8 = args.no_cpu = args.no_c5 = args.no_mla = True
+        args.no_sparse = args.no_next = args.no_strong = True
+    return args
 
 
 def spawn_ranks(n: int) -> int:
@@ -547,6 +562,10 @@ def main():
     # ---------------------------------------------------------------- headline: C2
     # Measured last: the sections above have brought the chip to its steady clock (a cold
     # start reads 10-15 % low for the first ~0.1 s of back-to-back launches).
+    # Its inputs come from a generator of their own, so they are the same from run to run
+    # whichever of the sections above ran.
+    g = torch.Generator(device=dev)
+    g.manual_seed(4321 + rank)
     q, k, v = (uniform((B, H, S, D), torch.float16) for _ in range(3))
     o = torch.empty((B, H, S, D), dtype=torch.float32, device=dev)
     l = torch.empty((B, H, S), dtype=torch.float16, device=dev)
@@ -632,6 +651,9 @@ def main():
                      "kernel": kname, "kernel_ms": round(kernel_ms, 4)},
         **result,
     }
+    if args.dump_outputs:
+        sfx = "" if rank == 0 else f".rank{rank}"
+        dump_outputs(args.dump_outputs, {"O" + sfx: o, "L" + sfx: l})
     del q, k, v, o, l
 
     # ---------------------------------------------------------------- CPU baseline
@@ -673,6 +695,26 @@ def fake_device_run(args, world: int, rank: int):
                           "data": "none (--fake-device)"}), flush=True)
     if world > 1:
         dist_.destroy_process_group()
+
+
+DUMP_BYTES = 56 << 20  # --dump-outputs budget over all arrays (float32)
+
+
+def dump_outputs(path: str, tensors: dict):
+    """Write each tensor as path/<name>.npy in float32.  When the arrays together exceed
+    DUMP_BYTES, each is cut to its proportional share: a fixed, seeded sample of its flattened
+    elements (sorted indices from numpy's default_rng(0), the same for every run of a shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for t in tensors.values())
+    budget = DUMP_BYTES // 4
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=keep))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def pmc_record(kernel: str, S: int, H: int, D: int) -> dict:

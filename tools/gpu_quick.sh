@@ -1,6 +1,7 @@
 #!/bin/bash
 # Quick GPU iteration: selected GPU tests, then a reduced bench line.
-# Usage: bash tools/gpu_quick.sh TAG "pytest selection" "bench flags"
+# Usage: bash tools/gpu_quick.sh TAG "pytest selection" "bench flags"   (bench flags: --full
+# for the side rows, trimmed with --no-*)
 set -o pipefail
 TAG=$1; SEL=$2; BFLAGS=$3
 OUT=gpurun_out/$TAG

@@ -8,7 +8,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-me
 rc=$?
 tail -3 "$OUT/pytest.log"
 [ $rc -eq 0 ] || { echo "pytest rc=$rc: stopping"; exit $rc; }
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
 python - <<'PY'
 import json
 b = json.load(open("gpurun_out/r06m/bench.json"))

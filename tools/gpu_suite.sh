@@ -12,6 +12,6 @@ timeout -k 10 900 python -u -m pytest $SEL -m gpu -q --timeout 300 --timeout-met
 rc=$?
 tail -15 "$OUT/pytest.log"
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || { echo "pytest rc=$rc: stopping"; exit $rc; }
-timeout -k 10 300 python -u bench.py --steps 20 > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 20 > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 exit $rc
