@@ -255,7 +255,18 @@ typedef struct mfa_attention_buffers {
 } mfa_attention_buffers_t;
 
 /* MultiHeadAttention.forward / encodeForward (MultiHeadAttention.swift:33-83, :197-234,
- * dispatchBatched :255-384): grid (ceil(R/Bp), H, B), writes O and L. */
+ * dispatchBatched :255-384): grid (ceil(R/Bp), H, B), writes O and L.
+ * Decode steps on an FP16 / BF16 K/V cache (few query rows per kv head reading many keys)
+ * run the split-KV decode kernels instead: the keys are split over workgroups, each K/V byte
+ * is read once per kv head for the whole GQA group, and a merge launch follows when a head's
+ * keys are split (its partials live in library scratch).  Eligible: Q/K/V of one 16-bit type
+ * with dense, 16-byte aligned rows (contiguous BHSD, or strided caches such as BSHD whose
+ * strides are multiples of 8 elements, K and V with the same row stride), D % 8 == 0 and
+ * D <= 256, a positive scale, untransposed operands, no additive mask or sparse ranges
+ * (causal and sliding-window masks are served, the latter when no row is masked everywhere),
+ * each head's K/V extent below 2^31 bytes.  The route is taken for shapes where it measured
+ * faster (DESIGN.md §3 "16-bit decode"); other calls run the kernels they ran before.  The
+ * result is deterministic and independent of strides.  mfa_multihead_plan reports the route. */
 mfa_status_t mfa_multihead_forward(const mfa_multihead_descriptor_t* desc,
                                    const mfa_attention_buffers_t* buffers, void* stream);
 

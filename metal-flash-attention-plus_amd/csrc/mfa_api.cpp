@@ -283,10 +283,57 @@ bool fwd2_eligible(const mfa::FwdParams& p, int elem, int DP, int kvsrc) {
   return p.q.sd == 1 && p.k.sd == 1 && p.v.sd == 1 && p.o_sd == 1;
 }
 
+// The split-KV decode kernels on an FP16 / BF16 K/V cache (attention_decode.hip, SRC_SAME): few
+// query rows per kv head reading many keys.  Q/K/V of one 16-bit type with dense, 16-byte
+// aligned rows (contiguous BHSD, or BSHD-strided caches whose strides are multiples of 8
+// elements; K and V with the same row stride), D % 8 == 0, D <= 256, a positive scale, dense O
+// rows, no mask but causal or a window that leaves no row empty (the rules of decode_eligible).
+// Routed by default where it was measured faster than the 128-row kernels (DESIGN.md §3,
+// "16-bit decode"): at least kKv16MinKeys keys read and at most 16 rows per kv head (the 16-row
+// form), or up to kKv16MaxRows rows (the 32-row form, which streams K/V once per 32-row tile)
+// when the GQA group has at least kKv16MinGroup query heads: the 128-row kernels read K/V once
+// per query head, so without a group they read no more than the 32-row form does.
+// MFA_DECODE_KV16=0: never; =1: at any eligible size (tests, A/B).
+constexpr int kKv16MaxRows = 64;
+constexpr int kKv16MinKeys = 4096;
+constexpr int kKv16MinGroup = 4;
+bool decode_kv16_eligible(const mfa::FwdParams& p, int elem) {
+  const char* sw = mfa::dev_env("MFA_DECODE_KV16");
+  if (sw && sw[0] == '0') return false;
+  if (elem != 1 && elem != 2) return false;
+  const int prec = elem == 1 ? MFA_PRECISION_FP16 : MFA_PRECISION_BF16;
+  if (p.q.prec != prec || p.k.prec != prec || p.v.prec != prec) return false;
+  if (p.D % 8 != 0 || p.D > 256 || p.C <= 0 || !(p.c_log2 > 0.f)) return false;
+  if (p.mask.amask || p.mask.ranges || (p.mask.window && !p.mask.skip_ok)) return false;
+  if (p.q.sd != 1 || p.k.sd != 1 || p.v.sd != 1 || p.o_sd != 1) return false;
+  if (!p.q.vec || !p.k.vec || !p.v.vec || p.k.ss != p.v.ss) return false;
+  // Per-head K/V byte ranges are addressed with 32-bit buffer offsets, including the row
+  // offsets of a whole 32-key tile at the last key.
+  if (((int64_t)p.C + 32) * p.k.ss * 2 >= ((int64_t)1 << 31)) return false;
+  if (sw && sw[0] == '1') return true;
+  const int64_t rows = (int64_t)(p.H / p.Hkv) * p.R;
+  if (rows > 16 && (rows > kKv16MaxRows || p.H / p.Hkv < kKv16MinGroup)) return false;
+  return mfa::decode_keys(p.R, p.C, p.mask.causal) >= kKv16MinKeys;
+}
+
 hipError_t launch_forward(const mfa::FwdParams& p, int elem, int DP, int kvsrc, hipStream_t s) {
   if (DP == kBigD) return mfa::fwd_bigd_dispatch(p, elem, s);
   if (const char* e = mfa::dev_env("MFA_DISABLE_FAST")) {
     if (e[0] == '1') return mfa::fwd_dispatch(p, elem, DP, kvsrc, kvsrc, s);
+  }
+  if (kvsrc == 0 && decode_kv16_eligible(p, elem)) {
+    // The split partials live in library scratch slot 14 (no counters: nothing to zero); one
+    // split per unit merges in LDS and needs none (decode_workspace_bytes returns 0).
+    void* ws = nullptr;
+    const size_t wsb = mfa::decode_workspace_bytes(p.B, p.Hkv, (p.H / p.Hkv) * p.R,
+                                                   mfa::decode_keys(p.R, p.C, p.mask.causal), p.D);
+    bool have = true;
+    if (wsb && mfa::plan_capture()) ws = (void*)kPlanDummy;
+    else if (wsb) have = scratch(wsb, &ws, 14, s) == MFA_SUCCESS;
+    if (have) {
+      const hipError_t e = mfa::fwd_decode_dispatch(p, elem, ws, s);
+      if (e != hipErrorNotSupported) return e;
+    }
   }
   if (fwd2_eligible(p, elem, DP, kvsrc)) {
     // Causal shapes with enough work take the stream-split kernel, which needs a workspace

@@ -63,8 +63,9 @@ inline int bigd_lds_bytes(int kind, int elem) {
 }
 hipError_t fwd_bigd_dispatch(const FwdParams& p, int elem, hipStream_t stream);
 hipError_t bwd_bigd_dispatch(const BwdParams& p, int kind, int elem, hipStream_t stream);
-// Split-KV decode forward for per-tensor INT8 K/V (attention_decode.hip) and the workspace it
-// needs (partials of every wave).
+// Split-KV decode forward (attention_decode.hip) for per-tensor INT8 / INT4 K/V, or K/V stored
+// in the 16-bit compute type (p.k.prec == elem), and the workspace it needs (one partial per
+// split and row; 0 when one split per unit merges in LDS).
 size_t decode_workspace_bytes(int B, int Hkv, int rows, int C, int D);
 int decode_keys(int R, int C, bool causal);
 hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hipStream_t stream);

@@ -80,7 +80,8 @@ struct BwdParams {
   MaskArgs mask;
 };
 
-// Split-KV decode forward (attention_decode.hip): INT8 K/V, few query rows per kv head.
+// Split-KV decode forward (attention_decode.hip): INT8 / INT4 / 16-bit K/V, few query rows per
+// kv head.
 struct DecodeParams {
   FwdParams f;
   int32_t rows;      // query rows per kv head: (H / H_kv) · R
