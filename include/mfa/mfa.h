@@ -631,6 +631,14 @@ int mfa_release_scratch(void* stream);
 /* Diagnostics: (kernel, device) pairs whose dynamic-LDS attribute the library has set. */
 int mfa_kernel_attribute_count(void);
 
+/* Diagnostics: the step order of the causal forward's mirrored block pairs.  A pair whose
+ * light block has at most the returned number of 64-key tiles runs the heavy block's own tiles
+ * first and the shared tiles last; 0: every pair runs the shared tiles first.  mirrored: the
+ * mirrored-pair kernel (not the adjacent pairs); kv_source: K/V as the caller stored them, 0 =
+ * 16-bit, 1 = INT8, 2 = INT4 (widened on load or by the dequantisation pass: both keep the
+ * first order and stay bit-identical); sparse_ranges: the call has a sparse-range mask. */
+int mfa_forward_order_tiles(int mirrored, int kv_source, int sparse_ranges);
+
 #ifdef __cplusplus
 }
 #endif

@@ -955,8 +955,268 @@ __device__ __forceinline__ void fwd2_share_body(const FwdParams& p) {
 #undef QKV_LOAD
 #undef QKV_WIDEN
 
+// Own-tiles-first order of a mirrored pair (16-bit K/V).  For a pair whose light block A has
+// few key tiles, A-first costs a prologue that lands Q of both blocks, a switch that stores A's
+// O while group 1 stands at the step barrier, and a two-barrier merge, all on the workgroups
+// that end last.  Here the steps run the other way round:
+//   own-tile steps 0..h0-1: both groups with B's rows, group 0 on B's tiles [nA, nA + h0),
+//     group 1 on [nA + h0, nB), each in its own ring (today's phase 2);
+//   the park (group 0, start of step h0): its partial state of B (O, m, lh) goes to LDS the
+//     shared steps do not touch — O over group 1's ring, m and lh over the wave's Q staging
+//     region once A's Q (staged there by DMA during step h0 - 1) is in registers;
+//   shared steps h0..h0+nA-1: tiles [0, nA) in ring 0, group 0 with A's rows, group 1 with B's;
+//   the fold: group 1 combines the parked state with its own (the merge's arithmetic; the park
+//     is at least one step barrier old), then both groups leave through O row images.
+// The prologue stages B's Q once (each wave half of its 32 rows, both groups read them) and
+// each group's first tile, V still in flight at the first QK^T when there are two or more own
+// steps.  Whether a workgroup runs this order: fwd2_own_first_pair.
+template <int BK>
+__device__ __forceinline__ bool fwd2_own_first_pair(const FwdParams& p) {
+  if (p.own_first <= 0) return false;
+  const int pi = blockIdx.x / (p.B * p.H);
+  const int rbA = pi, rbB = p.nblk - 1 - pi;
+  if (rbA >= rbB) return false;  // the odd middle block has no A
+  int a0, a1, b0, b1;
+  key_range(p, rbA * 128, 128, BK, &a0, &a1);
+  key_range(p, rbB * 128, 128, BK, &b0, &b1);
+  if (a0 != b0 || a1 <= a0 || b1 <= b0) return false;
+  const int nA = (a1 - a0 + BK - 1) / BK, nB = (b1 - b0 + BK - 1) / BK;
+  return nA <= p.own_first && nB > nA;
+}
+
+template <class E, int DP, int BK, bool NTS>
+__device__ __forceinline__ void fwd2_share_own_first_body(const FwdParams& p) {
+  constexpr int NT = 256, BQ = 128, ND = DP / 32;
+  constexpr int TILEB = BK * DP * 2;
+  constexpr int QW = 32 * DP * 2;       // one wave's 32 Q rows
+  constexpr int ORS = DP * 4 + 16;      // O row image pitch
+  constexpr int PARKB = 4 * ND * 16 * 64 * 4;  // group 0's parked O
+  static_assert(PARKB <= 4 * TILEB, "the parked O fits group 1's ring");
+  static_assert(2 * 64 * 4 <= QW, "the parked m and lh fit the wave's Q staging region");
+  static_assert(2 * BQ * ORS <= 8 * TILEB + 4 * QW, "both O row images fit the kernel's LDS");
+  static_assert(8 * TILEB + 4 * QW <= 160 * 1024, "LDS");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x;
+  const int g = __builtin_amdgcn_readfirstlane(tid / NT);
+  const int gt = tid % NT;
+  const int lane = tid & 63, wg = gt >> 6;
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int rbase[2] = {TileA<DP>::row_base(l32, hh, 0), TileA<DP>::row_base(l32, hh, 1)};
+  const int trb[2] = {TileA<DP>::tr_base(lane, 0), TileA<DP>::tr_base(lane, 1)};
+  char* const sk = smem;                   // ring 0: group 0's own tiles, then the shared tiles
+  char* const sv = smem + 2 * TILEB;
+  char* const kb0 = smem + g * 4 * TILEB;  // this group's ring in the own-tile steps
+  char* const vb0 = kb0 + 2 * TILEB;
+  char* const qstg = smem + 8 * TILEB + wg * QW;
+  // The wave's slice of the park (group 0 writes, group 1's wave of the same rows reads).
+  float4* const park = reinterpret_cast<float4*>(smem + 4 * TILEB) + wg * ND * 4 * 64;
+  float* const pml = reinterpret_cast<float*>(qstg);
+
+  const int BH = p.B * p.H;
+  const int pi = blockIdx.x / BH, bh = blockIdx.x % BH;
+  const int b = bh / p.H, h = bh % p.H, kvh = h % p.Hkv;
+  const float c = p.c_log2;
+  const int wsz = 0x3fffffff;
+  MFA_STAMP(0);
+  MFA_CYC(0);
+  if (pi >= p.pro_split)
+    for (int i = 0; i < p.pro_delay; ++i) __builtin_amdgcn_s_sleep(8);
+
+  DmaA<DP, BK, NT> kd, vd;         // a group's own tiles
+  DmaA<DP, BK, 2 * NT> ksh, vsh;   // shared tiles, staged by all 8 waves
+  DmaA<DP, 16, 64> qd;             // half of the wave's 32 Q rows (the other group's wave: the rest)
+  const char* khead = (const char*)p.k.ptr + ((int64_t)b * p.k.sb + (int64_t)kvh * p.k.sh) * 2;
+  const char* vhead = (const char*)p.v.ptr + ((int64_t)b * p.v.sb + (int64_t)kvh * p.v.sh) * 2;
+  const char* qhead = (const char*)p.q.ptr + ((int64_t)b * p.q.sb + (int64_t)h * p.q.sh) * 2;
+  kd.init((int)p.k.ss * 2, p.C, p.D * 2, gt);
+  vd.init((int)p.v.ss * 2, p.C, p.D * 2, gt);
+  ksh.init((int)p.k.ss * 2, p.C, p.D * 2, tid);
+  vsh.init((int)p.v.ss * 2, p.C, p.D * 2, tid);
+  qd.init((int)p.q.ss * 2, p.R, p.D * 2, lane);
+
+  const int rbA = pi, rbB = p.nblk - 1 - pi;
+  int a0, a1, b0, b1;
+  key_range(p, rbA * BQ, BQ, BK, &a0, &a1);
+  key_range(p, rbB * BQ, BQ, BK, &b0, &b1);
+  const int nB = (b1 - b0 + BK - 1) / BK;
+  const int nA = (a1 - a0 + BK - 1) / BK;  // 0 < nA < nB, a0 == b0 (fwd2_own_first_pair)
+  const int h0 = (nB - nA + 1) / 2;        // own-tile steps (group 0's share of B's own tiles)
+  const int S = h0 + nA;
+  // This group's own tile at step s < h0; false past its range (group 1 may have one fewer).
+  auto own_tile = [&](int s, int& t) -> bool {
+    const int i = nA + s + (g == 1 ? h0 : 0);
+    t = b0 + i * BK;
+    return s < h0 && i < nB;
+  };
+  // Rows [r0 + 32 wg, + 32) of Q into this wave's staging region, half from each group's wave.
+  auto stage_q = [&](int r0) {
+    qd.issue(qhead, r0 + wg * 32 + g * 16, qstg + g * (QW / 2));
+  };
+
+  int q0 = rbB * BQ;
+  int qi = q0 + wg * 32 + l32;
+  i16x8 qf[DP / 16];
+  RowState<DP> st;
+  st.init();
+  using A = Arith16<E, DP>;
+  // Two or more own steps: V of the first tile stays in flight until step 0's PV.
+  const bool dv = h0 >= 2;
+  {
+    int t0;
+    const bool has0 = own_tile(0, t0);
+    if (has0) kd.issue(khead, t0, kb0);
+    stage_q(q0);
+    if (has0) vd.issue(vhead, t0, vb0);
+    constexpr int PV0 = DmaA<DP, BK, NT>::PPW;  // V pieces per wave (the youngest)
+    static_assert(PV0 < 16, "counted vmcnt");
+    if (dv && has0)
+      __builtin_amdgcn_s_waitcnt(0x0F70 | PV0);
+    else
+      wait_vm();
+    __syncthreads();
+#pragma unroll
+    for (int ds = 0; ds < DP / 16; ++ds) qf[ds] = A::read_row_a(qstg, rbase, 0, ds);
+    prescale_q2<E, DP>(qf, c);
+    // One own step: step 0 already stages A's Q over the rows just read.
+    if (!dv) __syncthreads();
+  }
+
+  auto step = [&](int s, auto first_c) {
+    constexpr bool FIRST = decltype(first_c)::value;  // step 0 with V still in flight
+    // A's Q during the last own step (older than the tile pieces below).
+    if (s == h0 - 1) stage_q(rbA * BQ);
+    // Stage the next step's tile(s) into the slot read two steps ago.
+    const int nx = (s + 1) & 1;
+    bool issued = false;
+    if (s + 1 < h0) {
+      int tn;
+      if (own_tile(s + 1, tn)) {
+        kd.issue(khead, tn, kb0 + nx * TILEB);
+        vd.issue(vhead, tn, vb0 + nx * TILEB);
+        issued = true;
+      }
+    } else if (s + 1 < S) {
+      const int tn = b0 + (s + 1 - h0) * BK;
+      ksh.issue(khead, tn, sk + nx * TILEB);
+      vsh.issue(vhead, tn, sv + nx * TILEB);
+    }
+    if (s == h0 && g == 0) {
+      // The park: group 1's ring and this wave's Q staging region are idle from here on.
+      MFA_STAMP(4);
+#pragma unroll
+      for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq)
+          park[(dt * 4 + gq) * 64 + lane] = make_float4(st.o[dt][4 * gq], st.o[dt][4 * gq + 1],
+                                                        st.o[dt][4 * gq + 2], st.o[dt][4 * gq + 3]);
+#pragma unroll
+      for (int ds = 0; ds < DP / 16; ++ds) qf[ds] = A::read_row_a(qstg, rbase, 0, ds);
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): A's Q is in registers
+      pml[lane] = st.m;
+      pml[64 + lane] = st.lh;
+      __asm__ __volatile__("" ::: "memory");
+      q0 = rbA * BQ;
+      qi = q0 + wg * 32 + l32;
+      prescale_q2<E, DP>(qf, c);
+      st.init();
+      MFA_STAMP(5);
+    }
+    const bool shared = s >= h0;
+    int tc = b0 + (s - h0) * BK;
+    const bool have = shared || own_tile(s, tc);
+    const char* kt = (shared ? sk : kb0) + (s & 1) * TILEB;
+    const char* vt = (shared ? sv : vb0) + (s & 1) * TILEB;
+    const bool mask_tile = (tc + BK > p.C) || (p.mask.causal && tc + BK - 1 > q0);
+    if constexpr (FIRST) {
+      // V0 is older than the next own tile's pieces issued above.
+      constexpr int NPN = 2 * DmaA<DP, BK, NT>::PPW;
+      static_assert(NPN < 16, "counted vmcnt");
+      f32x16 sc[BK / 32];
+      i16x8 pb[BK / 16];
+      if (have) {
+        fwd2_qk<E, DP, BK>(kt, rbase, qf, st, sc);
+        fwd2_softmax<E, DP, BK>(st, sc, pb, tc, mask_tile, qi, p, c, wsz, hh);
+      }
+      if (issued)
+        __builtin_amdgcn_s_waitcnt(0x0F70 | NPN);
+      else
+        wait_vm();
+      __syncthreads();
+      if (have) fwd2_pv<E, DP, BK>(vt, trb, pb, st);
+    } else if (have) {
+      fwd2_tile<E, DP, BK>(kt, vt, rbase, trb, qf, st, tc, mask_tile, qi, p, c, wsz, hh);
+    }
+    wait_vm();
+    __syncthreads();
+  };
+  MFA_STAMP(1);
+  int s = 0;
+  if (dv) step(s++, std::true_type());
+  for (; s < h0; ++s) step(s, std::false_type());
+  MFA_STAMP(2);
+  for (; s < S; ++s) step(s, std::false_type());
+  MFA_STAMP(3);
+
+  // The fold (group 1: B's rows) and A's normalisation (group 0).
+  float lm = st.m;
+  float l;
+  if (g == 1) {
+    const float mb = pml[lane];
+    const float lb = pml[64 + lane];
+    const float mf = fmaxf(st.m, mb);
+    const float ca = __builtin_amdgcn_exp2f(st.m - mf);
+    const float cb = __builtin_amdgcn_exp2f(mb - mf);
+    l = cross_half_sum(st.lh * ca + lb * cb) + kFltMin;
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const float4 v = park[(dt * 4 + gq) * 64 + lane];
+        st.o[dt][4 * gq] = st.o[dt][4 * gq] * ca + v.x * cb;
+        st.o[dt][4 * gq + 1] = st.o[dt][4 * gq + 1] * ca + v.y * cb;
+        st.o[dt][4 * gq + 2] = st.o[dt][4 * gq + 2] * ca + v.z * cb;
+        st.o[dt][4 * gq + 3] = st.o[dt][4 * gq + 3] * ca + v.w * cb;
+      }
+    lm = mf;
+  } else {
+    l = cross_half_sum(st.lh) + kFltMin;
+  }
+  if (!(l > 0.f)) l = kFltMin;
+  const float inv = p.o_mul / l;
+  if (hh == 0 && qi < p.R) store_l(p, lm + __log2f(l), b, h, qi);
+  __syncthreads();  // the park has been read: the images go over it and the rings
+  // Both blocks leave through O row images as whole rows from all 8 waves.
+  char* orow = smem + (g * BQ + wg * 32 + l32) * ORS;
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq)
+      *reinterpret_cast<float4*>(orow + (dt * 32 + 8 * gq + 4 * hh) * 4) =
+          make_float4(st.o[dt][4 * gq] * inv, st.o[dt][4 * gq + 1] * inv,
+                      st.o[dt][4 * gq + 2] * inv, st.o[dt][4 * gq + 3] * inv);
+  __syncthreads();
+  float* obase = p.o + (int64_t)b * p.o_sb + (int64_t)h * p.o_sh;
+#pragma unroll
+  for (int blk = 0; blk < 2; ++blk) {
+    const int qb = (blk ? rbB : rbA) * BQ;
+    store_o_image<DP, BQ, 2 * NT, NTS>(p, obase, smem + blk * BQ * ORS, ORS, qb, tid,
+                                       qb + BQ <= p.R && p.D == DP);
+  }
+  MFA_CYC(1);
+  MFA_STAMP_DRAIN();
+  MFA_STAMP(7);
+}
+
 template <class E, int DP, int BK, bool MIRROR, bool NTS = false, bool IMG = false, bool DV = false>
 __global__ void __launch_bounds__(512, 2) mfa_fwd2_share_kernel(FwdParams p) {
+  // The routed mirrored kernel carries both orders; the choice is uniform over the workgroup.
+  if constexpr (MIRROR && NTS && IMG && DV) {
+    if (fwd2_own_first_pair<BK>(p)) {
+      fwd2_share_own_first_body<E, DP, BK, NTS>(p);
+      return;
+    }
+  }
   fwd2_share_body<E, DP, BK, MIRROR, NTS, IMG, DV, SRC_SAME>(p);
 }
 
@@ -982,6 +1242,23 @@ static void set_prologue_delay(FwdParams& q, int npairs) {
   q.pro_split = ds ? atoi(ds) : npairs / 2;
 }
 
+// Mirrored pairs: the order of a pair's steps.  Pairs whose light block has at most this many
+// key tiles run B's own tiles first (fwd2_share_own_first_body); 0 keeps the shared tiles first
+// everywhere.  Only the mirrored 16-bit K/V kernel has the second order: the adjacent pairs
+// (sparse ranges included) and the INT8 / INT4 on-load kernel keep the first, and so does a call
+// whose 16-bit K/V are the dequantisation pass's copy of INT8 / INT4 operands (kv_src is the
+// stored class): the pass path and the on-load kernel stay bit-identical.
+// MFA_FWD_ORDER=<tiles> sets the threshold (0: off; development A/B and tests).
+constexpr int kFwdOwnFirstTiles = 10;
+int fwd_own_first_tiles(bool mirrored, int kv_src, bool sparse_ranges) {
+  if (!mirrored || kv_src != SRC_SAME || sparse_ranges) return 0;
+  if (const char* e = mfa::dev_env("MFA_FWD_ORDER")) {
+    const int t = atoi(e);
+    return t > 0 ? t : 0;
+  }
+  return kFwdOwnFirstTiles;
+}
+
 template <class E, int DP, int BK, bool MIRROR = true>
 static hipError_t launch_fwd2_share(const FwdParams& p, hipStream_t stream) {
   // Adjacent pairs use ring 0 only (every step is shared, no merge).
@@ -1000,6 +1277,7 @@ static hipError_t launch_fwd2_share(const FwdParams& p, hipStream_t stream) {
     q.xcd_heads = !(xh && xh[0] == '0');
   }
   set_prologue_delay(q, npairs);
+  q.own_first = fwd_own_first_tiles(MIRROR, p.kv_stored, p.mask.ranges != nullptr);
   // Mirrored pairs store the final O image non-temporally; MFA_SHARE_NT=0 keeps plain stores
   // (A/B).
   // Mirrored pairs: deferred V0 (+1.2 % at C2 in one-process A/B) and non-temporal O image

@@ -416,6 +416,10 @@ int mfa_release_scratch(void* stream) {
 
 int mfa_kernel_attribute_count(void) { return (int)mfa::lds_attr_entries(); }
 
+int mfa_forward_order_tiles(int mirrored, int kv_source, int sparse_ranges) {
+  return mfa::fwd_own_first_tiles(mirrored != 0, kv_source, sparse_ranges != 0);
+}
+
 int mfa_operand_buffer_binding(mfa_operand_t operand) {
   switch (operand) {
     case MFA_OPERAND_Q: return 0;
@@ -972,6 +976,9 @@ extern "C" mfa_status_t mfa_quantized_forward(const mfa_quantized_descriptor_t* 
     if (kvsrc > 0) {
       if ((st = dequant_copy(&p.k, B, Hkv, C, D, elem, 6, s)) != MFA_SUCCESS) return st;
       if ((st = dequant_copy(&p.v, B, Hkv, C, D, elem, 7, s)) != MFA_SUCCESS) return st;
+      // The pass's copy holds the operands the on-load kernels widen: the 16-bit kernel keeps
+      // their step order for it, so both paths go on computing the same bits.
+      p.kv_stored = kvsrc;
       kvsrc = 0;
     }
     if (is_quantized(qp) && (st = dequant_copy(&p.q, B, H, R, D, elem, 8, s)) != MFA_SUCCESS)

@@ -82,6 +82,9 @@ hipError_t fwd_stream_dispatch(const FwdParams& p, int elem, int DP, hipStream_t
 // Software-pipelined fp16 D = 128 forward (attention_fwd_pipe.hip); hipErrorNotSupported when
 // the shape or mask is not covered.
 hipError_t fwd_pipe_dispatch(const FwdParams& p, int elem, int DP, hipStream_t stream);
+// Mirrored causal pairs: light-block key tiles up to which a pair runs its own tiles first
+// (attention_fwd_v2.hip; 0 for every kernel without that order).
+int fwd_own_first_tiles(bool mirrored, int kv_src, bool sparse_ranges);
 // Second-generation 16-bit forward (attention_fwd_v2.hip).
 hipError_t fwd2_dispatch(const FwdParams& p, int elem, int DP, hipStream_t stream);
 // Dense 16-bit copy [B, Hx, S, D] of a quantised operand holding the MFMA operands the

@@ -56,6 +56,13 @@ struct FwdParams {
   // 512 shader cycles before their prologue loads, so the heavy pairs' prologue burst (the
   // kernel's critical path) has HBM to itself.
   int32_t pro_delay, pro_split;
+  // ... and the pairs whose light block has at most own_first key tiles run B's own tiles
+  // first and the shared tiles last (0: every pair runs the shared tiles first).
+  int32_t own_first;
+  // K/V as the caller stored them when p.k / p.v are the dequantisation pass's 16-bit copy
+  // (SrcKind: SRC_I8 / SRC_I4; 0: the operands as passed).  Such a call keeps the step order
+  // of the INT8 / INT4 on-load kernel, which computes the same bits from the stored bytes.
+  int32_t kv_stored;
 };
 
 struct BwdParams {

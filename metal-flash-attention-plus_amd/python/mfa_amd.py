@@ -382,6 +382,7 @@ _sig("mfa_last_error", ctypes.c_char_p, [])
 _sig("mfa_abi_version", ctypes.c_int, [])
 _sig("mfa_release_scratch", ctypes.c_int, [ctypes.c_void_p])
 _sig("mfa_kernel_attribute_count", ctypes.c_int, [])
+_sig("mfa_forward_order_tiles", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int])
 _sig("mfa_operand_buffer_binding", ctypes.c_int, [ctypes.c_int])
 _sig("mfa_attention_descriptor_init", None, [_P(AttentionDescriptor)])
 _sig("mfa_attention_kernel_descriptor", ctypes.c_int,
