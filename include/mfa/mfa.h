@@ -478,6 +478,70 @@ mfa_status_t mfa_quantized_plan(const mfa_quantized_descriptor_t* desc, mfa_kern
                                 const mfa_quantized_tensor_t* key,
                                 const mfa_quantized_tensor_t* value, mfa_kernel_plan_t* out);
 
+/* ---------------------------------------------------------------------------------- */
+/* Paged, ragged KV-cache decode.  (No reference counterpart: the reference attends over */
+/* dense K/V tensors with one sequence length per call.)                                 */
+
+/* A K/V cache held in fixed-size pages.  Sequence b's keys 0 .. seq_lens[b] - 1 lie in
+ * logical pages 0, 1, ...; logical page j of sequence b is pool page
+ * block_table[b * max_pages_per_seq + j].  Both pools share one layout.  block_table and
+ * seq_lens are device memory and are read by the kernels only, never by the host, so a call
+ * stays asynchronous and a captured graph can be replayed with new lengths and tables.
+ * What the kernels do with out-of-range device values: seq_lens[b] is clamped to
+ * [0, min(max_seq_len, max_pages_per_seq * page_size)], and every page id to
+ * [0, num_pages - 1] — a wrong table entry reads wrong data, never memory outside the pools.
+ * A contiguous cache is the special case of one page per sequence: a dense BHSD or BSHD
+ * [B, ., C_alloc, D] tensor with C_alloc a power of two is strides = {batch stride, head stride,
+ * row stride}, page_size = C_alloc, max_pages_per_seq = 1, num_pages = B, block_table[b] = b. */
+typedef struct mfa_paged_kv_cache {
+  const void* k_pool;            /* device; page p, kv head h, slot t, element d at
+                                    p*strides[0] + h*strides[1] + t*strides[2] + d (elements) */
+  const void* v_pool;            /* same layout and strides as k_pool */
+  int64_t strides[3];            /* page, kv head, token slot — element strides; d contiguous */
+  int32_t precision;             /* MFA_PRECISION_FP16 / BF16 (the query's type) / INT8; INT4
+                                    pools are not supported yet (MFA_ERR_UNSUPPORTED) */
+  float k_scale, v_scale;        /* per-tensor, INT8 only: x = scale * (q - zero_point) */
+  int32_t k_zero_point, v_zero_point; /* INT8 only, in [-128, 128] */
+  const int32_t* block_table;    /* device [batch][max_pages_per_seq]: pool page of logical page j */
+  const int32_t* seq_lens;       /* device [batch]: keys of each sequence */
+  uint32_t page_size;            /* keys per page: a power of two, >= 32 */
+  uint32_t max_pages_per_seq;
+  uint32_t num_pages;            /* pages in the pools */
+} mfa_paged_kv_cache_t;
+
+typedef struct mfa_paged_decode_descriptor {
+  mfa_attention_descriptor_t base;   /* precision of Q, scale, sparsity (NONE or CAUSAL), L precision */
+  uint32_t batch_size, num_heads, num_kv_heads;
+  uint32_t rows;                     /* R: query rows per head */
+  uint32_t head_dim;
+  uint32_t max_seq_len;              /* host-side bound on seq_lens[]; sizes the split and the workspace */
+} mfa_paged_decode_descriptor_t;
+
+/* Split-KV decode forward over a paged cache.  query: [B, H, R, D] in the descriptor's 16-bit
+ * type (query_strides: optional 4-entry BHSD element strides, NULL = contiguous, d contiguous);
+ * output: dense FP32 [B, H, R, D]; logsumexp: nullable [B, H, R], FP16 when
+ * low_precision_intermediates, else FP32.  Query head h reads kv head h % num_kv_heads.
+ * Masks: MFA_SPARSITY_NONE — row q of sequence b attends to keys 0 .. seq_lens[b] - 1;
+ * MFA_SPARSITY_CAUSAL — row q attends to keys j <= seq_lens[b] - R + q: the KV-cache
+ * convention (the R new tokens are already appended and the last row sees every key), which
+ * differs from the top-left diagonal of mfa_multihead_forward (key <= query index) and needs
+ * seq_lens[b] >= R.  Sliding windows and sparse masks: MFA_ERR_UNSUPPORTED.
+ * A sequence of length 0 gets output rows of exact zeros (for INT8 pools with v_scale < 4) and
+ * L = -FLT_MAX in FP32, -inf in FP16: finite or -inf, never NaN.
+ * Supported: D % 8 == 0 (INT8: D % 16 == 0), D <= 256; 16-byte aligned pools, query and strides
+ * (in bytes), token stride below 2^24 bytes; B * H_kv * ceil((H / H_kv) * R / 32) < 65536; a
+ * positive softmax scale (and k_scale); min(max_seq_len, max_pages_per_seq * page_size) <= 2^30.
+ * batch_size == 0 or rows == 0 succeeds and launches nothing.  The split-KV partials live in
+ * library scratch (mfa_release_scratch), sized by max_seq_len. */
+mfa_status_t mfa_paged_decode_forward(const mfa_paged_decode_descriptor_t* desc,
+                                      const void* query, const int64_t* query_strides,
+                                      const mfa_paged_kv_cache_t* cache,
+                                      float* output, void* logsumexp, void* stream);
+/* The kernels that call launches (see mfa_multihead_plan).  cache == NULL plans a 16-bit cache
+ * of 256-key pages; NULL pointers inside a cache plan aligned buffers. */
+mfa_status_t mfa_paged_decode_plan(const mfa_paged_decode_descriptor_t* desc,
+                                   const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
+
 /* GPU runtime quantization (GEMMQuantization.swift:305-623 semantics, bit-exact; the
  * reference does this on the CPU in QuantizedTensor.from, :720-860).
  * input: device tensor of `count` elements in `input_precision` (FP32/FP16/BF16), viewed as

@@ -69,6 +69,11 @@ hipError_t bwd_bigd_dispatch(const BwdParams& p, int kind, int elem, hipStream_t
 size_t decode_workspace_bytes(int B, int Hkv, int rows, int C, int D);
 int decode_keys(int R, int C, bool causal);
 hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hipStream_t stream);
+// The same kernels over a paged, ragged cache (16-bit or per-tensor INT8 pools): p.C is the
+// host-side cap on every sequence's length, which sizes the split and the workspace
+// (decode_workspace_bytes of that cap).
+hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int elem,
+                                     void* workspace, hipStream_t stream);
 // FP16 Q with per-tensor INT8 / INT4 K/V (src SRC_I8 / SRC_I4) widened on load inside the
 // shared-tile loop (attention_fwd_kv8.hip); D <= 128 padded to 128, no masks.
 hipError_t fwd_kv8_dispatch(const FwdParams& p, int elem, int DP, int src, hipStream_t stream);

@@ -100,6 +100,23 @@ struct DecodeParams {
   int32_t fused;     // nsplit == 1: the workgroup merges its 4 waves' partials in LDS
 };
 
+// Paged, ragged K/V cache of the paged decode kernels (attention_decode.hip).  f.k.ptr / f.v.ptr
+// are the pools, f.k.ss the token-slot stride (elements), f.C the host-side cap on every length;
+// the key count of batch item b and the pool page of each of its logical pages are device values.
+struct PagedKv {
+  const int32_t* block_table;  // [B][max_pages]: pool page of logical page j (clamped when read)
+  const int32_t* seq_lens;     // [B]: keys of each sequence (clamped to [0, f.C] when read)
+  int64_t page_bytes;          // byte stride between pool pages
+  int64_t head_bytes;          // byte stride between the kv heads of one page
+  int32_t lg_page;             // log2(keys per page); pages hold whole 32-key tiles
+  int32_t max_pages;           // block-table row length
+  int32_t num_pages;           // pages in the pools
+};
+struct PagedDecodeParams {
+  DecodeParams d;
+  PagedKv pg;
+};
+
 // MFMA GEMM (gemm.hip): C = A·B (+C); two (B, C) pairs share A when b[1] != nullptr.
 struct GemmParams {
   const void* a;

@@ -367,6 +367,65 @@ class MLADescriptor(ctypes.Structure):
     ]
 
 
+class PagedKVCache(ctypes.Structure):
+    """mfa_paged_kv_cache_t: K/V pools in fixed-size pages, a device block table and device
+    sequence lengths (no reference counterpart)."""
+    _fields_ = [
+        ("k_pool", ctypes.c_void_p),
+        ("v_pool", ctypes.c_void_p),
+        ("strides", ctypes.c_int64 * 3),
+        ("precision", ctypes.c_int32),
+        ("k_scale", ctypes.c_float),
+        ("v_scale", ctypes.c_float),
+        ("k_zero_point", ctypes.c_int32),
+        ("v_zero_point", ctypes.c_int32),
+        ("block_table", ctypes.c_void_p),
+        ("seq_lens", ctypes.c_void_p),
+        ("page_size", ctypes.c_uint32),
+        ("max_pages_per_seq", ctypes.c_uint32),
+        ("num_pages", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, precision, page_size, max_pages_per_seq, num_pages, num_kv_heads, head_dim,
+             k_pool=None, v_pool=None, block_table=None, seq_lens=None, strides=None,
+             k_scale=1.0, v_scale=1.0, k_zero_point=0, v_zero_point=0):
+        """Pools [num_pages, num_kv_heads, page_size, head_dim] unless `strides` (page, kv head,
+        token slot; elements) says otherwise.  Tensors may be None for a plan query."""
+        c = cls()
+        c.k_pool, c.v_pool = _ptr(k_pool), _ptr(v_pool)
+        c.block_table, c.seq_lens = _ptr(block_table), _ptr(seq_lens)
+        if strides is None:
+            strides = (num_kv_heads * page_size * head_dim, page_size * head_dim, head_dim)
+        c.strides = (ctypes.c_int64 * 3)(*[int(x) for x in strides])
+        c.precision = int(precision)
+        c.k_scale, c.v_scale = float(k_scale), float(v_scale)
+        c.k_zero_point, c.v_zero_point = int(k_zero_point), int(v_zero_point)
+        c.page_size, c.max_pages_per_seq, c.num_pages = page_size, max_pages_per_seq, num_pages
+        c._keep = (k_pool, v_pool, block_table, seq_lens)  # the struct holds raw device pointers
+        return c
+
+
+class PagedDecodeDescriptor(ctypes.Structure):
+    _fields_ = [
+        ("base", AttentionDescriptor),
+        ("batch_size", ctypes.c_uint32),
+        ("num_heads", ctypes.c_uint32),
+        ("num_kv_heads", ctypes.c_uint32),
+        ("rows", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("max_seq_len", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, base: AttentionDescriptor, B, H, R, D, max_seq_len, Hkv=None):
+        d = cls()
+        d.base = base
+        d.batch_size, d.num_heads, d.num_kv_heads = B, H, H if Hkv is None else Hkv
+        d.rows, d.head_dim, d.max_seq_len = R, D, max_seq_len
+        return d
+
+
 def _sig(name, restype, argtypes):
     fn = getattr(lib, name, None)
     if fn is None:
@@ -416,6 +475,10 @@ _sig("mfa_quantized_backward_query", ctypes.c_int,
 _sig("mfa_quantized_backward_key_value", ctypes.c_int,
      [_P(QuantizedDescriptor), _P(QuantizedTensor), _P(QuantizedTensor), _P(QuantizedTensor),
       _V, _V, _V, _V, _V, _V])
+_sig("mfa_paged_decode_forward", ctypes.c_int,
+     [_P(PagedDecodeDescriptor), _V, _P(ctypes.c_int64), _P(PagedKVCache), _V, _V, _V])
+_sig("mfa_paged_decode_plan", ctypes.c_int,
+     [_P(PagedDecodeDescriptor), _P(PagedKVCache), _P(KernelPlan)])
 _sig("mfa_quantize_workspace_size", ctypes.c_size_t,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32])
 _sig("mfa_quantize", ctypes.c_int,
@@ -638,6 +701,26 @@ class QuantizedAttention:
             ctypes.byref(desc), ctypes.byref(query), ctypes.byref(key), ctypes.byref(value),
             _ptr(grad_output), _ptr(logsumexp), _ptr(d_values), _ptr(grad_key),
             _ptr(grad_value), _stream(stream)))
+
+
+def paged_decode_forward(desc: PagedDecodeDescriptor, query, cache: PagedKVCache, output,
+                         logsumexp=None, query_strides=None, stream=None):
+    """mfa_paged_decode_forward: split-KV decode over a paged, ragged K/V cache.  query
+    [B, H, R, D] 16-bit, output FP32 [B, H, R, D]; the lengths and the block table stay on the
+    device, so the call can be captured in a graph and replayed with new values."""
+    s = _strides(query_strides)
+    check(lib.mfa_paged_decode_forward(ctypes.byref(desc), _ptr(query), s[0] if s else None,
+                                       ctypes.byref(cache), _ptr(output), _ptr(logsumexp),
+                                       _stream(stream)))
+
+
+def paged_decode_plan(desc: PagedDecodeDescriptor, cache: Optional[PagedKVCache] = None) -> list[dict]:
+    """mfa_paged_decode_plan: the kernels paged_decode_forward launches (see multihead_plan);
+    without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
+    out = KernelPlan()
+    check(lib.mfa_paged_decode_plan(ctypes.byref(desc), None if cache is None else ctypes.byref(cache),
+                                    ctypes.byref(out)))
+    return out.as_list()
 
 
 def quantize(x, target: Precision, mode: QuantMode = QuantMode.tensorWise, rows=None, cols=None,
