@@ -542,6 +542,53 @@ mfa_status_t mfa_paged_decode_forward(const mfa_paged_decode_descriptor_t* desc,
 mfa_status_t mfa_paged_decode_plan(const mfa_paged_decode_descriptor_t* desc,
                                    const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
 
+typedef struct mfa_paged_append_descriptor {
+  int32_t  input_precision;   /* MFA_PRECISION_FP16 / BF16: type of the new key/value rows */
+  uint32_t batch_size, num_kv_heads;
+  uint32_t rows;              /* R: new-token rows per sequence in key/value (upper bound when new_lens is given) */
+  uint32_t head_dim;
+  uint32_t max_seq_len;       /* same meaning as in mfa_paged_decode_descriptor_t */
+} mfa_paged_append_descriptor_t;
+
+/* Appends new K/V rows to a paged cache on the device: the write side of
+ * mfa_paged_decode_forward.  key / value: [B, H_kv, R, D] in input_precision (key_strides /
+ * value_strides: optional 4-entry BHSD element strides, NULL = contiguous; d contiguous, every
+ * stride a non-negative multiple of 8 elements, 16-byte aligned bases; K and V may differ).  The
+ * [B, R, H_kv * D] output of a fused projection is strides = {R*H_kv*D, D, H_kv*D, 1}.
+ * Where a row goes: cache->seq_lens[b] is the length AFTER the append — the value the following
+ * mfa_paged_decode_forward reads, matching its CAUSAL convention ("the R new tokens are already
+ * appended"); the order on a stream is seq_lens += R, append, decode.  With
+ * n_b = new_lens ? clamp(new_lens[b], 0, R) : R (new_lens: device [B], nullable; a ragged prefill
+ * chunk in one call), row r < n_b of sequence b is key position t = seq_lens[b] - n_b + r: slot
+ * t mod page_size of pool page clamp(block_table[b * max_pages_per_seq + t / page_size], 0,
+ * num_pages - 1), every kv head of the row, at the cache's three strides.
+ * What is never written: rows r >= n_b; rows whose t lies outside
+ * [0, min(max_seq_len, max_pages_per_seq * page_size)); any byte other than the D elements of a
+ * written (row, kv head); seq_lens, block_table and new_lens.  A wrong table entry or length
+ * writes to the wrong page, never outside the pools — the reader's guarantee, for writes.
+ * The function writes through cache->k_pool / v_pool: the struct's const is the reader's view.
+ * 16-bit pools must be of input_precision and receive the bits unchanged.  INT8 pools receive
+ * q = clamp(round_half_away(x / scale) + zero_point, -128, 127) with k_scale / k_zero_point for
+ * K and v_* for V, x / scale the IEEE FP32 quotient of the exactly widened input: the bytes of
+ * mfa_quantize's per-element arithmetic, which the decode kernels dequantise.  Both scales must
+ * be finite and > 0 (stricter than the reader, which never divides by them), zero points in
+ * [-128, 128].  INT4 pools: MFA_ERR_UNSUPPORTED.
+ * The cache struct is checked by the reader's rules (page size a power of two >= 32; strides
+ * >= 0 and multiples of 16 bytes; token stride >= D and below 2^24 bytes; D % 8 == 0 (INT8:
+ * D % 16 == 0), D <= 256; min(max_seq_len, max_pages_per_seq * page_size) <= 2^30; 16-byte
+ * aligned pools), and B * R < 2^31.  batch_size == 0 or rows == 0 succeeds and launches nothing.
+ * Asynchronous on `stream`: no host read of device memory, no scratch, no synchronisation; valid
+ * under stream capture, so seq_lens += R, append and decode replay as one graph. */
+mfa_status_t mfa_paged_kv_append(const mfa_paged_append_descriptor_t* desc,
+                                 const void* key, const void* value,
+                                 const int64_t* key_strides, const int64_t* value_strides,
+                                 const int32_t* new_lens,
+                                 const mfa_paged_kv_cache_t* cache, void* stream);
+/* The kernel that call launches (see mfa_multihead_plan).  cache == NULL plans a 16-bit cache of
+ * 256-key pages in input_precision; NULL pointers inside a cache plan aligned buffers. */
+mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descriptor_t* desc,
+                                      const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
+
 /* GPU runtime quantization (GEMMQuantization.swift:305-623 semantics, bit-exact; the
  * reference does this on the CPU in QuantizedTensor.from, :720-860).
  * input: device tensor of `count` elements in `input_precision` (FP32/FP16/BF16), viewed as

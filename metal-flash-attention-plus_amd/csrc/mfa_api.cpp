@@ -2005,3 +2005,141 @@ extern "C" mfa_status_t mfa_paged_decode_plan(const mfa_paged_decode_descriptor_
   if (st == MFA_SUCCESS) scope.copy_to(out);
   return st;
 }
+
+// =========================================================================================
+// The write side of the paged cache (paged_append.hip): new key / value rows to their slots in
+// the pools, addressed on the device from seq_lens (the lengths after the append), new_lens and
+// the block table.  One launch, no scratch, nothing read on the host.  The cache struct is
+// checked by paged_decode's rules, restated here (that function's checks are interleaved with
+// the query's and keep their messages).
+namespace {
+
+mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void* key,
+                          const void* value, const int64_t* key_strides,
+                          const int64_t* value_strides, const int32_t* new_lens,
+                          const mfa_paged_kv_cache_t* cache, hipStream_t stream) {
+  const char* const what = "paged append";
+  if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
+  const int64_t B = desc->batch_size, Hkv = desc->num_kv_heads;
+  const int64_t R = desc->rows, D = desc->head_dim;
+  if (Hkv == 0 || D == 0 || desc->max_seq_len == 0 || cache->max_pages_per_seq == 0 ||
+      cache->num_pages == 0)
+    return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: empty shape", what);
+  const uint32_t ps = cache->page_size;
+  if (ps < 32 || (ps & (ps - 1)) != 0)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: page size %u is not a power of two >= 32", what, ps);
+  const int iprec = desc->input_precision;
+  if (iprec != MFA_PRECISION_FP16 && iprec != MFA_PRECISION_BF16)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: input precision %d (FP16 or BF16)", what, iprec);
+  const int cprec = cache->precision;
+  if (cprec != MFA_PRECISION_INT8 && cprec != MFA_PRECISION_FP16 && cprec != MFA_PRECISION_BF16)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: cache precision %d (FP16, BF16 or INT8)", what, cprec);
+  const bool i8 = cprec == MFA_PRECISION_INT8;
+  if (!i8 && cprec != iprec)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: 16-bit cache precision %d differs from the input's %d",
+                what, cprec, iprec);
+  if (D % (i8 ? 16 : 8) != 0 || D > 256)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of %d, at most 256)",
+                what, (long long)D, i8 ? 16 : 8);
+  if (i8) {
+    for (const float s : {cache->k_scale, cache->v_scale})
+      if (!(s > 0.f) || !std::isfinite(s))
+        return fail(MFA_ERR_UNSUPPORTED, "%s: scale %g is not finite and positive", what, (double)s);
+    if (cache->k_zero_point < -128 || cache->k_zero_point > 128 || cache->v_zero_point < -128 ||
+        cache->v_zero_point > 128)
+      return fail(MFA_ERR_UNSUPPORTED, "%s: zero point outside [-128, 128]", what);
+  }
+  const int es = i8 ? 1 : 2;
+  for (int i = 0; i < 3; ++i)
+    if (cache->strides[i] < 0 || (cache->strides[i] * es) % 16 != 0)
+      return fail(MFA_ERR_UNSUPPORTED, "%s: cache stride %d is not a multiple of 16 bytes", what, i);
+  if (cache->strides[2] < D || cache->strides[2] * es >= ((int64_t)1 << 24))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: token stride %lld", what, (long long)cache->strides[2]);
+  if (B * R >= ((int64_t)1 << 31))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: too many rows", what);
+  const int64_t cap = std::min<int64_t>(desc->max_seq_len, (int64_t)cache->max_pages_per_seq * ps);
+  if (cap > ((int64_t)1 << 30))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: more than 2^30 keys per sequence", what);
+  if ((int64_t)cache->max_pages_per_seq * B >= ((int64_t)1 << 31) || cache->num_pages > 0x7fffffffu)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: block table too large", what);
+  if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to write; the buffers may be null
+  if (!key || !value || !cache->k_pool || !cache->v_pool || !cache->block_table ||
+      !cache->seq_lens)
+    return fail(MFA_ERR_INVALID_ARGUMENT,
+                "%s requires key, value, both pools, block_table and seq_lens", what);
+  if (!aligned16(cache->k_pool) || !aligned16(cache->v_pool))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: pools must be 16-byte aligned", what);
+
+  mfa::PagedAppendParams p;
+  memset(&p, 0, sizeof(p));
+  const int64_t dense[4] = {Hkv * R * D, R * D, D, 1};
+  for (int i = 0; i < 2; ++i) {
+    const void* src = i ? value : key;
+    const int64_t* s = i ? value_strides : key_strides;
+    if (!s) s = dense;
+    if (s[3] != 1 || !aligned16(src))
+      return fail(MFA_ERR_UNSUPPORTED, "%s: %s rows must be dense and 16-byte aligned", what,
+                  i ? "value" : "key");
+    for (int j = 0; j < 3; ++j)
+      if (s[j] < 0 || s[j] % 8 != 0)
+        return fail(MFA_ERR_UNSUPPORTED, "%s: %s stride %d is not a multiple of 8 elements", what,
+                    i ? "value" : "key", j);
+    p.src[i] = src;
+    p.s_sb[i] = s[0] * 2; p.s_sh[i] = s[1] * 2; p.s_ss[i] = s[2] * 2;
+    p.pool[i] = const_cast<void*>(i ? cache->v_pool : cache->k_pool);
+    p.scale[i] = i8 ? (i ? cache->v_scale : cache->k_scale) : 1.f;
+    p.zp[i] = i8 ? (i ? cache->v_zero_point : cache->k_zero_point) : 0;
+  }
+  p.pg.block_table = cache->block_table;
+  p.pg.seq_lens = cache->seq_lens;
+  p.pg.page_bytes = cache->strides[0] * es;
+  p.pg.head_bytes = cache->strides[1] * es;
+  p.pg.lg_page = __builtin_ctz(ps);
+  p.pg.max_pages = (int)cache->max_pages_per_seq;
+  p.pg.num_pages = (int)cache->num_pages;
+  p.new_lens = new_lens;
+  p.tok_bytes = cache->strides[2] * es;
+  p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
+  p.cap = (int)cap;
+  p.rows_total = (int)(B * R);
+  return hip_status(mfa::paged_append_dispatch(p, iprec, i8, stream), "mfa_paged_kv_append launch");
+}
+
+}  // namespace
+
+extern "C" mfa_status_t mfa_paged_kv_append(const mfa_paged_append_descriptor_t* desc,
+                                            const void* key, const void* value,
+                                            const int64_t* key_strides,
+                                            const int64_t* value_strides, const int32_t* new_lens,
+                                            const mfa_paged_kv_cache_t* cache, void* stream) {
+  return paged_append(desc, key, value, key_strides, value_strides, new_lens, cache,
+                      (hipStream_t)stream);
+}
+
+extern "C" mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descriptor_t* desc,
+                                                 const mfa_paged_kv_cache_t* cache,
+                                                 mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  memset(out, 0, sizeof(*out));
+  mfa_paged_kv_cache_t c;
+  if (cache) {
+    c = *cache;
+  } else {
+    // A dense 16-bit cache in the input's type, 256-key pages.
+    memset(&c, 0, sizeof(c));
+    c.precision = desc->input_precision;
+    c.k_scale = c.v_scale = 1.f;
+    c.page_size = 256;
+    c.max_pages_per_seq = (desc->max_seq_len + 255) / 256;
+    c.num_pages = std::max<uint32_t>(1, c.max_pages_per_seq * desc->batch_size);
+    c.strides[2] = desc->head_dim;
+    c.strides[1] = (int64_t)c.page_size * desc->head_dim;
+    c.strides[0] = c.strides[1] * desc->num_kv_heads;
+  }
+  fill_dummy(c.k_pool); fill_dummy(c.v_pool); fill_dummy(c.block_table); fill_dummy(c.seq_lens);
+  CaptureScope scope;
+  const mfa_status_t st = paged_append(desc, (const void*)kPlanDummy, (const void*)kPlanDummy,
+                                       nullptr, nullptr, nullptr, &c, nullptr);
+  if (st == MFA_SUCCESS) scope.copy_to(out);
+  return st;
+}

@@ -74,6 +74,11 @@ hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hi
 // (decode_workspace_bytes of that cap).
 hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int elem,
                                      void* workspace, hipStream_t stream);
+// The write side of that cache (paged_append.hip): one launch scatters the new key and value
+// rows (16-bit, type `elem`) into 16-bit pools of the same type or, with i8, quantises them into
+// per-tensor INT8 pools.
+hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8,
+                                 hipStream_t stream);
 // FP16 Q with per-tensor INT8 / INT4 K/V (src SRC_I8 / SRC_I4) widened on load inside the
 // shared-tile loop (attention_fwd_kv8.hip); D <= 128 padded to 128, no masks.
 hipError_t fwd_kv8_dispatch(const FwdParams& p, int elem, int DP, int src, hipStream_t stream);

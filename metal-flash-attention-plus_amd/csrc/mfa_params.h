@@ -117,6 +117,21 @@ struct PagedDecodeParams {
   PagedKv pg;
 };
 
+// Append to a paged cache (paged_append.hip): index 0 of each pair is the key, 1 the value.
+struct PagedAppendParams {
+  const void* src[2];          // new rows [B, H_kv, R, D], 16-bit, d contiguous
+  void* pool[2];               // the page pools (pg's layout; 16-bit of the source type, or INT8)
+  int64_t s_sb[2], s_sh[2], s_ss[2];  // BYTE strides of the sources: batch, kv head, row
+  PagedKv pg;                  // seq_lens: the lengths after the append
+  const int32_t* new_lens;     // [B] rows to append per sequence (clamped to [0, R]); NULL: R
+  int64_t tok_bytes;           // byte stride between the token slots of a page
+  float scale[2];              // INT8 pools: q = clamp(round(x / scale) + zp, -128, 127)
+  int32_t zp[2];
+  int32_t Hkv, R, D;
+  int32_t cap;                 // positions at or past it are dropped: min(max_seq_len, table span)
+  int32_t rows_total;          // B · R
+};
+
 // MFMA GEMM (gemm.hip): C = A·B (+C); two (B, C) pairs share A when b[1] != nullptr.
 struct GemmParams {
   const void* a;

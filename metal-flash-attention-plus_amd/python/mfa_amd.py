@@ -426,6 +426,24 @@ class PagedDecodeDescriptor(ctypes.Structure):
         return d
 
 
+class PagedAppendDescriptor(ctypes.Structure):
+    _fields_ = [
+        ("input_precision", ctypes.c_int32),
+        ("batch_size", ctypes.c_uint32),
+        ("num_kv_heads", ctypes.c_uint32),
+        ("rows", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("max_seq_len", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, precision, B, Hkv, R, D, max_seq_len):
+        d = cls()
+        d.input_precision = int(precision)
+        d.batch_size, d.num_kv_heads, d.rows, d.head_dim, d.max_seq_len = B, Hkv, R, D, max_seq_len
+        return d
+
+
 def _sig(name, restype, argtypes):
     fn = getattr(lib, name, None)
     if fn is None:
@@ -479,6 +497,11 @@ _sig("mfa_paged_decode_forward", ctypes.c_int,
      [_P(PagedDecodeDescriptor), _V, _P(ctypes.c_int64), _P(PagedKVCache), _V, _V, _V])
 _sig("mfa_paged_decode_plan", ctypes.c_int,
      [_P(PagedDecodeDescriptor), _P(PagedKVCache), _P(KernelPlan)])
+_sig("mfa_paged_kv_append", ctypes.c_int,
+     [_P(PagedAppendDescriptor), _V, _V, _P(ctypes.c_int64), _P(ctypes.c_int64), _V,
+      _P(PagedKVCache), _V])
+_sig("mfa_paged_kv_append_plan", ctypes.c_int,
+     [_P(PagedAppendDescriptor), _P(PagedKVCache), _P(KernelPlan)])
 _sig("mfa_quantize_workspace_size", ctypes.c_size_t,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32])
 _sig("mfa_quantize", ctypes.c_int,
@@ -720,6 +743,32 @@ def paged_decode_plan(desc: PagedDecodeDescriptor, cache: Optional[PagedKVCache]
     out = KernelPlan()
     check(lib.mfa_paged_decode_plan(ctypes.byref(desc), None if cache is None else ctypes.byref(cache),
                                     ctypes.byref(out)))
+    return out.as_list()
+
+
+def paged_kv_append(desc: PagedAppendDescriptor, key, value, cache: PagedKVCache, new_lens=None,
+                    key_strides=None, value_strides=None, stream=None):
+    """mfa_paged_kv_append: the new rows key / value [B, H_kv, R, D] (16-bit) go to their slots
+    in the cache's pools; cache.seq_lens holds the lengths AFTER the append, new_lens (device
+    int32 [B], optional) the rows of each sequence.  Strides default to the tensors' own (a
+    BSHD view of a projection buffer works as it is).  Nothing is read on the host, so
+    lens += R, append, decode can be captured in one graph."""
+    ks = _strides(key.stride() if key_strides is None and hasattr(key, "stride") else key_strides)
+    vs = _strides(value.stride() if value_strides is None and hasattr(value, "stride")
+                  else value_strides)
+    check(lib.mfa_paged_kv_append(ctypes.byref(desc), _ptr(key), _ptr(value),
+                                  ks[0] if ks else None, vs[0] if vs else None, _ptr(new_lens),
+                                  ctypes.byref(cache), _stream(stream)))
+
+
+def paged_kv_append_plan(desc: PagedAppendDescriptor,
+                         cache: Optional[PagedKVCache] = None) -> list[dict]:
+    """mfa_paged_kv_append_plan: the kernel paged_kv_append launches (see multihead_plan);
+    without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
+    out = KernelPlan()
+    check(lib.mfa_paged_kv_append_plan(ctypes.byref(desc),
+                                       None if cache is None else ctypes.byref(cache),
+                                       ctypes.byref(out)))
     return out.as_list()
 
 
