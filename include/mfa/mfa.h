@@ -589,6 +589,59 @@ mfa_status_t mfa_paged_kv_append(const mfa_paged_append_descriptor_t* desc,
 mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descriptor_t* desc,
                                       const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
 
+typedef struct mfa_paged_prefill_descriptor {
+  mfa_attention_descriptor_t base;   /* precision of Q, scale, sparsity (NONE or CAUSAL), L precision */
+  uint32_t batch_size, num_heads, num_kv_heads;
+  uint32_t rows;                     /* R: query rows per sequence in `query` (upper bound when new_lens is given) */
+  uint32_t head_dim;
+  uint32_t max_seq_len;              /* same meaning as in mfa_paged_decode_descriptor_t */
+} mfa_paged_prefill_descriptor_t;
+
+/* Paged prefill: the forward pass of a prompt, or of a ragged chunk of prompts, over the paged
+ * cache its keys were appended to — the step between mfa_paged_kv_append and
+ * mfa_paged_decode_forward, taking the same `cache`, `new_lens` and `rows` as the append.
+ * query: [B, H, R, D] in the descriptor's 16-bit type (query_strides: optional 4-entry BHSD
+ * element strides, NULL = contiguous; d contiguous, rows 16-byte aligned; the [B, R, H * D]
+ * output of a fused projection is strides = {R*H*D, D, H*D, 1}); output: dense FP32
+ * [B, H, R, D]; logsumexp: nullable [B, H, R], FP16 when low_precision_intermediates, else FP32
+ * (library scratch when NULL).  Query head h reads kv head h % num_kv_heads.
+ * Lengths: len_b = clamp(cache->seq_lens[b], 0, min(max_seq_len, max_pages_per_seq * page_size))
+ * — the reader's clamp — is the length AFTER the chunk was appended; n_b = new_lens ?
+ * clamp(new_lens[b], 0, R) : R (new_lens: device [B], nullable).  Row q < n_b of sequence b is
+ * key position t_q = len_b - n_b + q, the slot mfa_paged_kv_append wrote its key to.
+ * Masks: MFA_SPARSITY_CAUSAL — row q attends to keys j <= t_q: the decode call's KV-cache
+ * convention, per sequence and ragged; with n_b == len_b it is a plain causal prompt prefill.
+ * MFA_SPARSITY_NONE — row q attends to keys 0 .. len_b - 1.  Sliding windows and sparse masks:
+ * MFA_ERR_UNSUPPORTED.
+ * Rows that are not a position of their sequence — q >= n_b; t_q < 0 because n_b > len_b; any row
+ * when len_b == 0 — have no visible key under either mask and get output rows of exact zeros and
+ * L = -FLT_MAX in FP32, -inf in FP16 (the decode call's empty-sequence result), never NaN.  So
+ * every row of output and logsumexp is written, for any device values.
+ * Safety: page ids are clamped to [0, num_pages - 1] and the table lookup to the sequence's row
+ * — a wrong entry or length reads wrong data, never memory outside the pools; no byte of an
+ * unused slot (past len_b in its page) or of a page the table does not name for the keys read is
+ * fetched.
+ * Supported: pools of the query's type (FP16 or BF16) — INT8 and INT4 pools return
+ * MFA_ERR_UNSUPPORTED (INT8 is the natural follow-up); D % 8 == 0, D <= 256; the cache struct by
+ * the reader's rules (page size a power of two >= 32; strides >= 0 and multiples of 16 bytes;
+ * token stride >= D and below 2^24 bytes; 16-byte aligned pools;
+ * min(max_seq_len, max_pages_per_seq * page_size) <= 2^30; max_pages_per_seq * B < 2^31); a
+ * positive softmax scale, untransposed operands; B * H * R < 2^31.
+ * batch_size == 0 or rows == 0 succeeds and launches nothing; the buffers may then be null.
+ * Asynchronous on `stream`: no host read of device memory, no synchronisation, no workspace other
+ * than the scratch L; valid under stream capture, so seq_lens += n, append and prefill replay as
+ * one graph with new lengths and new_lens.  A short chunk over a very long prefix (few rows,
+ * many keys) is the decode call's shape: this call does not split the keys. */
+mfa_status_t mfa_paged_prefill_forward(const mfa_paged_prefill_descriptor_t* desc,
+                                       const void* query, const int64_t* query_strides,
+                                       const int32_t* new_lens,
+                                       const mfa_paged_kv_cache_t* cache,
+                                       float* output, void* logsumexp, void* stream);
+/* The kernel that call launches (see mfa_multihead_plan).  cache == NULL plans a 16-bit cache of
+ * 256-key pages; NULL pointers inside a cache plan aligned buffers. */
+mfa_status_t mfa_paged_prefill_plan(const mfa_paged_prefill_descriptor_t* desc,
+                                    const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
+
 /* GPU runtime quantization (GEMMQuantization.swift:305-623 semantics, bit-exact; the
  * reference does this on the CPU in QuantizedTensor.from, :720-860).
  * input: device tensor of `count` elements in `input_precision` (FP32/FP16/BF16), viewed as

@@ -1,0 +1,263 @@
+// attention_prefill_paged.hip — ragged, multi-row causal forward over the paged K/V cache
+// (mfa_paged_prefill_forward; no reference counterpart): the attention step of a prompt, or a
+// chunk of one, whose keys are already in the page pools (mfa_paged_kv_append wrote them) behind a
+// prefix of earlier keys.  The read side's addressing is attention_decode.hip's (PagedKv), the
+// tile body is the tuned 16-bit forward's (attention_fwd2.h: fwd2_tile, RowState, load_q2,
+// store_o_l), unchanged.
+//
+// Rows and keys.  len_b = clamp(seq_lens[b], 0, cap) is the length AFTER the chunk was appended,
+// n_b = new_lens ? clamp(new_lens[b], 0, R) : R the rows of sequence b in `query`.  Row q < n_b is
+// key position t_q = len_b - n_b + q: causal rows attend to keys j <= t_q, unmasked rows to keys
+// 0 .. len_b - 1.  Rows with no visible key (q >= n_b, t_q < 0, len_b == 0) get exact zeros and
+// L = -FLT_MAX (-inf in FP16): every row of O and L is written whatever the device values are.
+//
+// One workgroup of 4 waves x 32 rows owns a 128-row query block of one (b, h).  What differs from
+// mfa_fwd2_kernel (attention_fwd_v2.hip):
+//   * len_b and n_b are scalar loads through the constant address space, once per workgroup; the
+//     mask sees the lane's key position t_q, the stores its row q; the key bound is len_b (a local
+//     copy of FwdParams with C = len_b);
+//   * a workgroup whose block has no live row writes the dead-row result and leaves before any K/V
+//     load;
+//   * tiles start at absolute keys that are multiples of BK, counted from key 0, whatever the
+//     page size: the order of the arithmetic, and so every bit of O and L, is the same for any
+//     paging of the same keys;
+//   * a tile is staged in 32-key segments (PagedDma): a page holds whole segments (page size a
+//     power of two >= 32), so each segment has one page id, one base and one range-checked buffer
+//     descriptor whose range ends at the rows below both len_b and the page's end — neither an
+//     unused slot nor a foreign page is fetched, rows past the range land as zeros (and are masked);
+//   * page ids are scalar loads from the block table issued one tile before their tile's DMA
+//     (two before its compute), the lookup clamped to the table row and the id clamped to the
+//     pools where it is used; all tile bookkeeping is wave-uniform.
+// Causal: the key loop ends at the block's last visible key, and the grid runs the heaviest
+// (last) row blocks of every (b, h) first; the lengths are device values, so a block past n_b
+// costs one early exit.
+//
+// Not here (DESIGN.md §3 "Paged prefill"): K/V tiles shared between the query heads of a kv
+// group, split-KV for a short chunk over a very long prefix (the decode call's shape), quantised
+// pools.
+#include "attention_fwd2.h"
+
+namespace mfa {
+
+namespace {
+
+// Uniform (scalar-path) loads of the device values.
+typedef const __attribute__((address_space(4))) int32_t* prefill_i32_ptr;
+
+// LDS-DMA of one [BK][DP] 16-bit tile of a paged head into the TileA image, in 32-key segments
+// with a base and a byte range each.  The piece geometry is DmaA's (mfa_stage.h): piece n is half
+// of 8-row block n / (DP/64), wave w issues pieces w + NW·i; a 32-row segment is four 8-row blocks,
+// so piece i of every wave lies in segment SEG(i) and its lane offset is relative to that
+// segment's first row.
+template <int DP, int BK, int NT>
+struct PagedDma {
+  static constexpr int NW = NT / 64;
+  static constexpr int PPRB = DP / 64;
+  static constexpr int NPIECE = BK * DP * 2 / 1024;
+  static constexpr int PPW = NPIECE / NW;
+  static constexpr int NSEG = BK / 32;
+  static_assert(DP % 64 == 0 && BK % 32 == 0 && NPIECE % NW == 0 && PPW >= 1, "DMA geometry");
+  static constexpr int seg_of(int i) { return (NW * i) / PPRB / 4; }
+  static constexpr bool uniform_segments() {
+    for (int i = 0; i < PPW; ++i)
+      if ((NW * i) / PPRB / 4 != (NW * i + NW - 1) / PPRB / 4) return false;
+    return true;
+  }
+  int w;
+  int off[PPW];
+
+  // step: bytes per token slot; rowbytes: valid bytes per row (D · 2); tid: thread index.
+  __device__ __forceinline__ void init(int step, int rowbytes, int tid) {
+    static_assert(uniform_segments(), "a wave's piece i must lie in one segment for every wave");
+    w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l = tid & 63;
+#pragma unroll
+    for (int i = 0; i < PPW; ++i) {
+      const int n = w + NW * i;
+      const int rblk = n / PPRB, sub = 2 * (n % PPRB) + (l >> 5);
+      const int r7 = (l & 31) >> 2;
+      const int ch = 4 * sub + ((l & 3) ^ ((2 * rblk + (r7 >> 2)) & 3));
+      off[i] = ch * 16 < rowbytes ? ((rblk & 3) * 8 + r7) * step + ch * 16 : 0x40000000;
+    }
+  }
+  // head + rel[s]: first row of segment s; bytes[s]: the bytes of it a load may touch.
+  __device__ __forceinline__ void issue(const char* head, const int64_t (&rel)[NSEG],
+                                        const int (&bytes)[NSEG], char* dst) const {
+#pragma unroll
+    for (int i = 0; i < PPW; ++i)
+      lds_dma16(head + rel[seg_of(i)], bytes[seg_of(i)], off[i], dst + (w + NW * i) * 1024);
+  }
+};
+
+// Block-table entry of the 32-key segment at key t (wave-uniform) of batch item b, as stored:
+// the lookup index is clamped to the table row (the look-ahead runs past the last tile), the id
+// is clamped to the pools by prefill_segment, where it is used.
+__device__ __forceinline__ int prefill_page(const PagedKv& pg, int b, int t) {
+  const int j = min(t >> pg.lg_page, pg.max_pages - 1);
+  return ((prefill_i32_ptr)pg.block_table)[(int64_t)b * pg.max_pages + j];
+}
+
+// Byte offset, from a head's first byte in the pool (pool + kv head offset), of the first row of
+// the 32-key segment at key t, and the bytes of the segment a load may touch: the rows below both
+// the sequence's length and the page's end (attention_decode.hip's kv_tile; 64-bit page offset).
+__device__ __forceinline__ int64_t prefill_segment(const PagedKv& pg, int page, int t, int len,
+                                                   int ssb, int rowbytes, int* bytes) {
+  const int pend = ((t >> pg.lg_page) + 1) << pg.lg_page;
+  const int rows = min(min(len, pend) - t, 32);
+  *bytes = rows > 0 ? (rows - 1) * ssb + rowbytes : 0;
+  const int id = min(max(page, 0), pg.num_pages - 1);
+  return (int64_t)id * pg.page_bytes + (int64_t)(t & ((1 << pg.lg_page) - 1)) * ssb;
+}
+
+// The result of a row with no visible key: zeros and L = -FLT_MAX (-inf once rounded to FP16),
+// in store_o_l's lane layout.
+template <int DP>
+__device__ __forceinline__ void store_dead_row(const FwdParams& p, int b, int h, int q, int hh) {
+  float* orow = p.o + (int64_t)b * p.o_sb + (int64_t)h * p.o_sh + (int64_t)q * p.o_ss;
+#pragma unroll
+  for (int dt = 0; dt < DP / 32; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d = dt * 32 + 8 * g + 4 * hh;
+      if (d < p.D) st_o4<false>(orow + d, 0.f, 0.f, 0.f, 0.f);
+    }
+  if (hh == 0) store_l(p, -kFltMax, b, h, q);
+}
+
+}  // namespace
+
+template <class E, int DP, int BK>
+__global__ void __launch_bounds__(256, 2) mfa_paged_prefill_kernel(PagedPrefillParams pp) {
+  constexpr int NT = 256, BQ = 128;
+  constexpr int TILEB = BK * DP * 2;
+  using Dma = PagedDma<DP, BK, NT>;
+  constexpr int NSEG = Dma::NSEG;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const kb0 = smem;
+  char* const vb0 = smem + 2 * TILEB;
+  const FwdParams& p = pp.f;
+  const PagedKv& pg = pp.pg;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int rbase[2] = {TileA<DP>::row_base(l32, hh, 0), TileA<DP>::row_base(l32, hh, 1)};
+  const int trb[2] = {TileA<DP>::tr_base(lane, 0), TileA<DP>::tr_base(lane, 1)};
+  // Causal: heaviest blocks first over the whole grid (balance); otherwise each head's blocks
+  // together on one XCD (L2 reuse of its K/V).
+  int bh, blk;
+  if (p.mask.causal) {
+    bh = blockIdx.x % (p.B * p.H);
+    blk = blockIdx.x / (p.B * p.H);
+  } else {
+    xcd_unit_block(blockIdx.x, p.B * p.H, p.nblk, &bh, &blk);
+  }
+  const int rb = p.nblk - 1 - blk;
+  const int b = bh / p.H, h = bh % p.H, kvh = h % p.Hkv;
+  const int q0 = rb * BQ;
+  const int q = q0 + wave * 32 + l32;
+
+  // The sequence's keys and rows (uniform).  p.C is the host-side cap on every length.
+  const int len = min(max(((prefill_i32_ptr)pg.seq_lens)[b], 0), p.C);
+  const int n = pp.new_lens ? min(max(((prefill_i32_ptr)pp.new_lens)[b], 0), p.R) : p.R;
+  const int shift = len - n;              // row q is key position shift + q
+  // Keys of this block: up to its last live row's position (causal), or all of them.
+  const int qlast = min(q0 + BQ, n) - 1;  // last row of the block that belongs to the sequence
+  const int kend = p.mask.causal ? min(len, shift + qlast + 1) : len;
+  if (q0 >= n || kend <= 0) {
+    // No live row: nothing of the cache is read.
+    if (q < p.R) store_dead_row<DP>(p, b, h, q, hh);
+    return;
+  }
+  const int tq = shift + q;
+  const bool live = q < n && tq >= 0;
+  // The body's view: len keys, the lane's query at key position tq (dead rows: masked wherever
+  // the causal mask is applied; their result is replaced below).
+  FwdParams lp = p;
+  lp.C = len;
+  const int qpos = live ? tq : -1;
+  const float c = p.c_log2;
+
+  const int ssb = (int)p.k.ss * 2, dbytes = 2 * p.D;
+  const char* khead = (const char*)p.k.ptr + (int64_t)kvh * pg.head_bytes;
+  const char* vhead = (const char*)p.v.ptr + (int64_t)kvh * pg.head_bytes;
+  Dma dma;  // K and V share the pool layout: one set of lane offsets
+  dma.init(ssb, dbytes, tid);
+  // Tile at key t with its segments' block-table entries `pages` into ring slot `slot`.
+  auto stage = [&](int t, const int (&pages)[NSEG], int slot) {
+    int64_t rel[NSEG];
+    int nb[NSEG];
+#pragma unroll
+    for (int s = 0; s < NSEG; ++s)
+      rel[s] = prefill_segment(pg, pages[s], t + 32 * s, len, ssb, dbytes, &nb[s]);
+    dma.issue(khead, rel, nb, kb0 + slot * TILEB);
+    dma.issue(vhead, rel, nb, vb0 + slot * TILEB);
+  };
+  int pgn[NSEG];  // entries of the next tile to stage
+#pragma unroll
+  for (int s = 0; s < NSEG; ++s) pgn[s] = prefill_page(pg, b, 32 * s);
+  stage(0, pgn, 0);
+#pragma unroll
+  for (int s = 0; s < NSEG; ++s) pgn[s] = prefill_page(pg, b, BK + 32 * s);
+
+  i16x8 qf[DP / 16];
+  load_q2<E, DP>(qf, p, b, h, q, live, hh, c);
+  RowState<DP> st;
+  st.init();
+  wait_vm();
+  __syncthreads();
+
+  int cur = 0;
+  for (int t = 0; t < kend; t += BK) {
+    if (t + BK < kend) {
+      stage(t + BK, pgn, cur ^ 1);
+      // The entries of the tile after it: a whole tile's compute before they are used.
+#pragma unroll
+      for (int s = 0; s < NSEG; ++s) pgn[s] = prefill_page(pg, b, t + 2 * BK + 32 * s);
+    }
+    // The block's first row bounds the tiles every live row sees whole.
+    const bool mask_tile = (t + BK > len) || (p.mask.causal && t + BK - 1 > shift + q0);
+    fwd2_tile<E, DP, BK>(kb0 + cur * TILEB, vb0 + cur * TILEB, rbase, trb, qf, st, t, mask_tile,
+                         qpos, lp, c, 0x3fffffff, hh);
+    wait_vm();
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  float l = cross_half_sum(st.lh) + kFltMin;
+  if (!(l > 0.f)) l = kFltMin;
+  if (live)
+    store_o_l<DP>(p, st.o, st.m, l, b, h, q, hh);
+  else if (q < p.R)
+    store_dead_row<DP>(p, b, h, q, hh);
+}
+
+// One launch; grid = (batch · heads · 128-row blocks).  p.C is the cap on every length, p.k / p.v
+// the pools (16-bit, the compute type), p.R the rows per sequence in the query.
+hipError_t fwd_prefill_paged_dispatch(const FwdParams& p, const PagedKv& pg,
+                                      const int32_t* new_lens, int elem, hipStream_t stream) {
+  if (p.k.prec != elem || p.v.prec != elem || p.k.ss != p.v.ss) return hipErrorNotSupported;
+  PagedPrefillParams pp;
+  pp.f = p;
+  pp.pg = pg;
+  pp.new_lens = new_lens;
+  pp.f.nblk = (p.R + 127) / 128;
+  const int64_t wgs = (int64_t)pp.f.nblk * p.B * p.H;
+  if (wgs >= ((int64_t)1 << 31)) return hipErrorNotSupported;
+  const dim3 grid((unsigned)wgs), block(256);
+  const int DP = p.D <= 64 ? 64 : p.D <= 128 ? 128 : 256;
+#define MFA_PREFILL(ELEM, EE, DPV, BKV)                                                       \
+  if (elem == ELEM && DP == DPV)                                                              \
+    return launch(mfa_paged_prefill_kernel<EE, DPV, BKV>, grid, block, 4 * BKV * DPV * 2,     \
+                  stream, pp);
+  MFA_PREFILL(P_FP16, F16, 64, 64)
+  MFA_PREFILL(P_FP16, F16, 128, 64)
+  MFA_PREFILL(P_FP16, F16, 256, 32)
+  MFA_PREFILL(P_BF16, BF16, 64, 64)
+  MFA_PREFILL(P_BF16, BF16, 128, 64)
+  MFA_PREFILL(P_BF16, BF16, 256, 32)
+#undef MFA_PREFILL
+  return hipErrorNotSupported;
+}
+
+}  // namespace mfa

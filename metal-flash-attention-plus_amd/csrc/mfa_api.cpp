@@ -2143,3 +2143,164 @@ extern "C" mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descript
   if (st == MFA_SUCCESS) scope.copy_to(out);
   return st;
 }
+
+// =========================================================================================
+// Paged prefill (attention_prefill_paged.hip): the R rows of each sequence in `query` — a prompt
+// or a chunk of one, ragged through new_lens — attend to the paged cache they were appended to.
+// One launch of 128-row query blocks, no workspace but the scratch L; lengths, row counts and the
+// block table are device values the host never reads.  The cache struct is checked by
+// paged_decode's rules, restated here with this call's messages; pools are 16-bit only.
+namespace {
+
+mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const void* query,
+                           const int64_t* query_strides, const int32_t* new_lens,
+                           const mfa_paged_kv_cache_t* cache, float* output, void* logsumexp,
+                           hipStream_t stream) {
+  const char* const what = "paged prefill";
+  if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
+  const mfa_attention_descriptor_t& base = desc->base;
+  const int64_t B = desc->batch_size, H = desc->num_heads, Hkv = desc->num_kv_heads;
+  const int64_t R = desc->rows, D = desc->head_dim;
+  if (H == 0 || Hkv == 0 || D == 0 || desc->max_seq_len == 0 || cache->max_pages_per_seq == 0 ||
+      cache->num_pages == 0)
+    return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: empty shape", what);
+  if (H % Hkv != 0)
+    return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: %lld heads over %lld kv heads", what,
+                (long long)H, (long long)Hkv);
+  const uint32_t ps = cache->page_size;
+  if (ps < 32 || (ps & (ps - 1)) != 0)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: page size %u is not a power of two >= 32", what, ps);
+  const int qprec = resolve_precisions(base).mem[MFA_OPERAND_Q];
+  const int elem = elem_of(qprec);
+  if (elem != 1 && elem != 2)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: query precision %d (FP16 or BF16)", what, qprec);
+  const int cprec = cache->precision;
+  if (cprec == MFA_PRECISION_INT8 || cprec == MFA_PRECISION_INT4)
+    return fail(MFA_ERR_UNSUPPORTED,
+                "%s: quantised pools (precision %d) are not supported; 16-bit pools only", what,
+                cprec);
+  if (cprec != MFA_PRECISION_FP16 && cprec != MFA_PRECISION_BF16)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: cache precision %d (FP16 or BF16)", what, cprec);
+  if (cprec != qprec)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: cache precision %d differs from the query's %d", what,
+                cprec, qprec);
+  if (D % 8 != 0 || D > 256)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of 8, at most 256)",
+                what, (long long)D);
+  if (base.has_sparse_mask || (base.sparsity_pattern != MFA_SPARSITY_NONE &&
+                               base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);
+  mfa_status_t st = check_transposes(base, false, what);
+  if (st != MFA_SUCCESS) return st;
+  const float scale = resolve_scale(base, (int)D);
+  if (!(scale > 0.f) || !(1.442695041f * scale > 0.f))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
+  for (int i = 0; i < 3; ++i)
+    if (cache->strides[i] < 0 || (cache->strides[i] * 2) % 16 != 0)
+      return fail(MFA_ERR_UNSUPPORTED, "%s: cache stride %d is not a multiple of 16 bytes", what, i);
+  // Row offsets inside a 32-key segment are 32-bit buffer offsets.
+  if (cache->strides[2] < D || cache->strides[2] * 2 >= ((int64_t)1 << 24))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: token stride %lld", what, (long long)cache->strides[2]);
+  if (B * H * R >= ((int64_t)1 << 31))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
+  if (B * H * ((R + 127) / 128) >= ((int64_t)1 << 31))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: the query blocks exceed the grid", what);
+  const int64_t cap = std::min<int64_t>(desc->max_seq_len, (int64_t)cache->max_pages_per_seq * ps);
+  if (cap > ((int64_t)1 << 30))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: more than 2^30 keys per sequence", what);
+  if ((int64_t)cache->max_pages_per_seq * B >= ((int64_t)1 << 31) || cache->num_pages > 0x7fffffffu)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: block table too large", what);
+  if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
+  if (!query || !output || !cache->k_pool || !cache->v_pool || !cache->block_table ||
+      !cache->seq_lens)
+    return fail(MFA_ERR_INVALID_ARGUMENT,
+                "%s requires query, output, both pools, block_table and seq_lens", what);
+  if (!aligned16(cache->k_pool) || !aligned16(cache->v_pool))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: pools must be 16-byte aligned", what);
+
+  mfa::FwdParams p;
+  memset(&p, 0, sizeof(p));
+  p.q = make_operand(query, qprec, (int)B, (int)H, (int)R, (int)D, query_strides, 0);
+  if (p.q.sd != 1 || !p.q.vec)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: query rows must be dense and 16-byte aligned", what);
+  // The pools as operands: only ptr, the token stride and the precision are read.
+  for (mfa::Operand* op : {&p.k, &p.v}) {
+    op->ptr = op == &p.k ? cache->k_pool : cache->v_pool;
+    op->ss = cache->strides[2];
+    op->sd = 1;
+    op->prec = cprec;
+    op->vec = 1;
+    op->scale = 1.f;
+    op->cols = (int)D;
+  }
+  p.o = output;
+  out_strides((int)R, (int)D, false, &p.o_ss, &p.o_sd);
+  p.o_sh = R * D;
+  p.o_sb = H * R * D;
+  p.l_f16 = resolve_precisions(base).mem[MFA_OPERAND_L] == MFA_PRECISION_FP16;
+  void* L = logsumexp;
+  if (!L) {
+    if (mfa::plan_capture()) L = (void*)kPlanDummy;
+    else if ((st = scratch((size_t)(B * H * R) * 4, &L, 0, stream)) != MFA_SUCCESS) return st;
+  }
+  p.l = L;
+  p.B = (int)B; p.H = (int)H; p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
+  p.C = (int)cap;
+  p.c_log2 = 1.442695041f * scale;
+  p.o_mul = 1.f;
+  p.mask.causal = base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
+  p.mask.skip_ok = 1;
+
+  mfa::PagedKv pg;
+  memset(&pg, 0, sizeof(pg));
+  pg.block_table = cache->block_table;
+  pg.seq_lens = cache->seq_lens;
+  pg.page_bytes = cache->strides[0] * 2;
+  pg.head_bytes = cache->strides[1] * 2;
+  pg.lg_page = __builtin_ctz(ps);
+  pg.max_pages = (int)cache->max_pages_per_seq;
+  pg.num_pages = (int)cache->num_pages;
+
+  const hipError_t e = mfa::fwd_prefill_paged_dispatch(p, pg, new_lens, elem, stream);
+  if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
+  return hip_status(e, "mfa_fwd (paged prefill) launch");
+}
+
+}  // namespace
+
+extern "C" mfa_status_t mfa_paged_prefill_forward(const mfa_paged_prefill_descriptor_t* desc,
+                                                  const void* query, const int64_t* query_strides,
+                                                  const int32_t* new_lens,
+                                                  const mfa_paged_kv_cache_t* cache, float* output,
+                                                  void* logsumexp, void* stream) {
+  return paged_prefill(desc, query, query_strides, new_lens, cache, output, logsumexp,
+                       (hipStream_t)stream);
+}
+
+extern "C" mfa_status_t mfa_paged_prefill_plan(const mfa_paged_prefill_descriptor_t* desc,
+                                               const mfa_paged_kv_cache_t* cache,
+                                               mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  memset(out, 0, sizeof(*out));
+  mfa_paged_kv_cache_t c;
+  if (cache) {
+    c = *cache;
+  } else {
+    // A dense 16-bit cache in the query's type, 256-key pages.
+    memset(&c, 0, sizeof(c));
+    c.precision = resolve_precisions(desc->base).mem[MFA_OPERAND_Q];
+    c.k_scale = c.v_scale = 1.f;
+    c.page_size = 256;
+    c.max_pages_per_seq = (desc->max_seq_len + 255) / 256;
+    c.num_pages = std::max<uint32_t>(1, c.max_pages_per_seq * desc->batch_size);
+    c.strides[2] = desc->head_dim;
+    c.strides[1] = (int64_t)c.page_size * desc->head_dim;
+    c.strides[0] = c.strides[1] * desc->num_kv_heads;
+  }
+  fill_dummy(c.k_pool); fill_dummy(c.v_pool); fill_dummy(c.block_table); fill_dummy(c.seq_lens);
+  CaptureScope scope;
+  const mfa_status_t st = paged_prefill(desc, (const void*)kPlanDummy, nullptr, nullptr, &c,
+                                        (float*)kPlanDummy, nullptr, nullptr);
+  if (st == MFA_SUCCESS) scope.copy_to(out);
+  return st;
+}

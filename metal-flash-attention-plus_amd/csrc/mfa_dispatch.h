@@ -74,6 +74,11 @@ hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hi
 // (decode_workspace_bytes of that cap).
 hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int elem,
                                      void* workspace, hipStream_t stream);
+// Ragged multi-row forward over the same cache, 16-bit pools of the compute type `elem`
+// (attention_prefill_paged.hip): one launch of 128-row query blocks, no workspace.  p.R is the
+// rows per sequence in the query, p.C the cap on every length; new_lens: device [B] or NULL.
+hipError_t fwd_prefill_paged_dispatch(const FwdParams& p, const PagedKv& pg,
+                                      const int32_t* new_lens, int elem, hipStream_t stream);
 // The write side of that cache (paged_append.hip): one launch scatters the new key and value
 // rows (16-bit, type `elem`) into 16-bit pools of the same type or, with i8, quantises them into
 // per-tensor INT8 pools.

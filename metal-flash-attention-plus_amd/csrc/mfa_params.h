@@ -117,6 +117,14 @@ struct PagedDecodeParams {
   PagedKv pg;
 };
 
+// Paged prefill (attention_prefill_paged.hip): f.R query rows per sequence attend to the paged
+// cache, row q < n_b of batch item b at key position len_b - n_b + q.
+struct PagedPrefillParams {
+  FwdParams f;                 // f.k / f.v: the pools (PagedKv's conventions); f.C: the length cap
+  PagedKv pg;                  // seq_lens: the lengths after the chunk was appended
+  const int32_t* new_lens;     // [B] rows of each sequence (clamped to [0, f.R]); NULL: f.R
+};
+
 // Append to a paged cache (paged_append.hip): index 0 of each pair is the key, 1 the value.
 struct PagedAppendParams {
   const void* src[2];          // new rows [B, H_kv, R, D], 16-bit, d contiguous

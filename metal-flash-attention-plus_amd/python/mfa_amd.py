@@ -426,6 +426,27 @@ class PagedDecodeDescriptor(ctypes.Structure):
         return d
 
 
+class PagedPrefillDescriptor(ctypes.Structure):
+    """mfa_paged_prefill_descriptor_t: R query rows per sequence over a paged cache."""
+    _fields_ = [
+        ("base", AttentionDescriptor),
+        ("batch_size", ctypes.c_uint32),
+        ("num_heads", ctypes.c_uint32),
+        ("num_kv_heads", ctypes.c_uint32),
+        ("rows", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("max_seq_len", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, base: AttentionDescriptor, B, H, R, D, max_seq_len, Hkv=None):
+        d = cls()
+        d.base = base
+        d.batch_size, d.num_heads, d.num_kv_heads = B, H, H if Hkv is None else Hkv
+        d.rows, d.head_dim, d.max_seq_len = R, D, max_seq_len
+        return d
+
+
 class PagedAppendDescriptor(ctypes.Structure):
     _fields_ = [
         ("input_precision", ctypes.c_int32),
@@ -497,6 +518,10 @@ _sig("mfa_paged_decode_forward", ctypes.c_int,
      [_P(PagedDecodeDescriptor), _V, _P(ctypes.c_int64), _P(PagedKVCache), _V, _V, _V])
 _sig("mfa_paged_decode_plan", ctypes.c_int,
      [_P(PagedDecodeDescriptor), _P(PagedKVCache), _P(KernelPlan)])
+_sig("mfa_paged_prefill_forward", ctypes.c_int,
+     [_P(PagedPrefillDescriptor), _V, _P(ctypes.c_int64), _V, _P(PagedKVCache), _V, _V, _V])
+_sig("mfa_paged_prefill_plan", ctypes.c_int,
+     [_P(PagedPrefillDescriptor), _P(PagedKVCache), _P(KernelPlan)])
 _sig("mfa_paged_kv_append", ctypes.c_int,
      [_P(PagedAppendDescriptor), _V, _V, _P(ctypes.c_int64), _P(ctypes.c_int64), _V,
       _P(PagedKVCache), _V])
@@ -743,6 +768,31 @@ def paged_decode_plan(desc: PagedDecodeDescriptor, cache: Optional[PagedKVCache]
     out = KernelPlan()
     check(lib.mfa_paged_decode_plan(ctypes.byref(desc), None if cache is None else ctypes.byref(cache),
                                     ctypes.byref(out)))
+    return out.as_list()
+
+
+def paged_prefill_forward(desc: PagedPrefillDescriptor, query, cache: PagedKVCache, output,
+                          new_lens=None, logsumexp=None, query_strides=None, stream=None):
+    """mfa_paged_prefill_forward: the R rows of each sequence in query [B, H, R, D] (16-bit)
+    attend to the paged cache they were appended to; cache.seq_lens holds the lengths AFTER the
+    append and new_lens (device int32 [B], optional) the rows of each sequence, as for
+    paged_kv_append.  Row q < new_lens[b] is key position seq_lens[b] - new_lens[b] + q; other
+    rows get zeros.  output FP32 [B, H, R, D].  Nothing is read on the host, so lens += n,
+    append, prefill can be captured in one graph."""
+    s = _strides(query_strides)
+    check(lib.mfa_paged_prefill_forward(ctypes.byref(desc), _ptr(query), s[0] if s else None,
+                                        _ptr(new_lens), ctypes.byref(cache), _ptr(output),
+                                        _ptr(logsumexp), _stream(stream)))
+
+
+def paged_prefill_plan(desc: PagedPrefillDescriptor,
+                       cache: Optional[PagedKVCache] = None) -> list[dict]:
+    """mfa_paged_prefill_plan: the kernel paged_prefill_forward launches (see multihead_plan);
+    without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
+    out = KernelPlan()
+    check(lib.mfa_paged_prefill_plan(ctypes.byref(desc),
+                                     None if cache is None else ctypes.byref(cache),
+                                     ctypes.byref(out)))
     return out.as_list()
 
 
