@@ -674,9 +674,14 @@ class MultiHeadAttention:
 
     def backward(self, desc: MultiHeadDescriptor, query, key, value, output, d_output,
                  logsumexp, d_query, d_key, d_value, d_buffer, mask=None, stream=None,
-                 phase: str = "both"):
+                 phase: str = "both", query_strides=None, key_strides=None,
+                 value_strides=None):
+        """query/key/value_strides: optional BHSD element strides of Q, K and V, as in forward;
+        O, dO and the gradients are dense."""
         b, keep = make_buffers(Q=query, K=key, V=value, O=output, dO=d_output, L=logsumexp,
-                               dQ=d_query, dK=d_key, dV=d_value, D=d_buffer, mask=mask)
+                               dQ=d_query, dK=d_key, dV=d_value, D=d_buffer, mask=mask,
+                               Q_strides=query_strides, K_strides=key_strides,
+                               V_strides=value_strides)
         fn = {"both": lib.mfa_multihead_backward, "query": lib.mfa_multihead_backward_query,
               "keyValue": lib.mfa_multihead_backward_key_value}[phase]
         check(fn(ctypes.byref(desc), ctypes.byref(b), _stream(stream)))

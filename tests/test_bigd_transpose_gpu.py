@@ -19,7 +19,7 @@ import torch
 
 import mfa_amd as mfa
 import oracle_lib as ol
-from harness import maxerr, seen, to_device
+from harness import assert_gradients_within_gate, gradient_gate, maxerr, seen, to_device
 
 pytestmark = pytest.mark.gpu
 FP32, FP16, BF16 = mfa.Precision.FP32, mfa.Precision.FP16, mfa.Precision.BF16
@@ -70,7 +70,10 @@ def run(Q, K, V, dO, prec, tr=(False, False, False, False), causal=False, window
             "dQ": back(dq, tr[0], R), "dK": back(dk, tr[1], C), "dV": back(dv, tr[2], C)}
 
 
-def check(got, ref, prec, S):
+def check(got, ref, prec, S, inputs=None, **mask):
+    """Absolute limits on every output and, for the 16-bit types, the relative gradient gate
+    of harness.py, built from the kernel-visible `inputs` (Q, K, V, dO) and the mask."""
+    assert (prec == FP32) == (inputs is None)
     if prec == FP32:
         tol = {"O": 2e-5, "L": 2e-5, "D": 2e-5, "dQ": 2e-5, "dK": 2e-5, "dV": 2e-5}
         tol = {k: v * max(1.0, S / 64) for k, v in tol.items()}
@@ -83,6 +86,9 @@ def check(got, ref, prec, S):
         assert np.isfinite(g).all(), f"{name} has non-finite values"
         e = maxerr(g, ref[name])
         assert e <= t, f"{name} max error {e:.3e} > {t:.3e}"
+    if prec != FP32:
+        gate = gradient_gate(*inputs, prec, ref, **mask)
+        assert_gradients_within_gate(got, ref, gate, report=f"{prec.name} D={inputs[0].shape[3]}")
 
 
 @pytest.mark.parametrize("D", [288, 320, 384, 512])
@@ -92,8 +98,9 @@ def test_large_head_dimension_fwd_bwd(gpu, D, prec):
     amp = 1.0 if prec == FP32 else 0.5
     Q, K, V, dO = (gaussian((B, H, S, D), 700 + i, amp) for i in range(4))
     got = run(Q, K, V, dO, prec)
-    ref = ol.attention(seen(Q, prec), seen(K, prec), seen(V, prec), dO=seen(dO, prec))
-    check(got, ref, prec, S)
+    vis = tuple(seen(x, prec) for x in (Q, K, V, dO))
+    ref = ol.attention(*vis[:3], dO=vis[3])
+    check(got, ref, prec, S, inputs=None if prec == FP32 else vis)
 
 
 @pytest.mark.parametrize("prec", [FP32, FP16])
@@ -107,9 +114,10 @@ def test_large_head_dimension_masks_gqa(gpu, prec, R, C, Hkv, causal, window):
     Q, dO = gaussian((B, H, R, D), 710, 0.5), gaussian((B, H, R, D), 711, 0.5)
     K, V = gaussian((B, Hkv, C, D), 712, 0.5), gaussian((B, Hkv, C, D), 713, 0.5)
     got = run(Q, K, V, dO, prec, causal=causal, window=window)
-    ref = ol.attention(seen(Q, prec), seen(K, prec), seen(V, prec), dO=seen(dO, prec),
-                       causal=causal, window=window)
-    check(got, ref, prec, max(R, C))
+    vis = tuple(seen(x, prec) for x in (Q, K, V, dO))
+    ref = ol.attention(*vis[:3], dO=vis[3], causal=causal, window=window)
+    check(got, ref, prec, max(R, C), inputs=None if prec == FP32 else vis, causal=causal,
+          window=window)
 
 
 ALL_TRANSPOSES = list(itertools.product([False, True], repeat=4))
@@ -134,8 +142,9 @@ def test_transposes_fwd_bwd_mixed(gpu, tr, prec, D):
     B, H, S = 1, 2, 200
     Q, K, V, dO = (gaussian((B, H, S, D), 730 + i, 0.5) for i in range(4))
     got = run(Q, K, V, dO, prec, tr=tr, causal=True)
-    ref = ol.attention(seen(Q, prec), seen(K, prec), seen(V, prec), dO=seen(dO, prec), causal=True)
-    check(got, ref, prec, S)
+    vis = tuple(seen(x, prec) for x in (Q, K, V, dO))
+    ref = ol.attention(*vis[:3], dO=vis[3], causal=True)
+    check(got, ref, prec, S, inputs=vis, causal=True)
 
 
 def test_transposed_equals_dense_bitwise(gpu):
@@ -190,3 +199,7 @@ def test_large_head_dimension_quantized(gpu, R, kv):
     assert maxerr(l, ref["L"]) < 7e-3 + 2.0 ** -11 * float(np.abs(ref["L"]).max())
     for name, t in (("dQ", dq), ("dK", dk), ("dV", dv)):
         assert maxerr(t, ref[name]) < 5e-2, name
+    # The relative gate: the emulation takes the dequantised K/V as its exact inputs.
+    gate = gradient_gate(Qd, kd, vd, dOd, FP16, ref)
+    assert_gradients_within_gate({"dQ": dq, "dK": dk, "dV": dv}, ref, gate,
+                                 report=f"{kv.name} R={R}")

@@ -11,7 +11,8 @@ import torch
 
 import mfa_amd as mfa
 import oracle_lib as ol
-from harness import maxerr, relerr, seen, to_device
+from harness import (assert_gradients_within_gate, gradient_gate, maxerr, relerr, seen,
+                     to_device)
 
 pytestmark = pytest.mark.gpu
 P = mfa.Precision
@@ -327,6 +328,12 @@ def test_quantized_backward_dequant_exact(gpu):
     assert maxerr(dvals, ref["D"]) < 1e-4
     for name, t in (("dQ", dq), ("dK", dk), ("dV", dv)):
         assert maxerr(t, ref[name]) < 5e-2, name
+    # The relative gate on the dequantised K/V as exact inputs.  L and D are FP32 here: the
+    # emulation rounds only P and dS, to the FP16 operand type, and dO, which is FP32 in
+    # memory here, where it becomes the FP16 operand of dP and dV (D keeps the FP32 values).
+    gate = gradient_gate(Qd, kd, vd, dO, P.FP16, ref, causal=True,
+                         low_precision_intermediates=False, round_dO=True)
+    assert_gradients_within_gate({"dQ": dq, "dK": dk, "dV": dv}, ref, gate, report="dequant")
 
 
 # ----------------------------------------------------------------------- dequantisation pass
@@ -434,6 +441,10 @@ def _quantized_backward_fast(kv, D, zps, S, monkeypatch, H=2, Hkv=2, window=None
                      f"mfa_bwd_kv_fast_kernel<F16, {D}, {32 if D == 256 else 64}, {src}, false>"], names
     for name, t in (("dQ", dq), ("dK", dk), ("dV", dv)):
         assert maxerr(t, ref[name]) < 5e-2 * max(1.0, np.abs(ref[name]).max()), name
+    # The relative gate on the dequantised K/V as exact inputs (L is FP16, D is BF16).
+    gate = gradient_gate(Qd, kd, vd, dOd, P.FP16, ref, causal=window is None, window=window)
+    assert_gradients_within_gate({"dQ": dq, "dK": dk, "dV": dv}, ref, gate,
+                                 report=f"{kv.name} D={D} S={S} H={H}/{Hkv}")
     if rows_per_kv < 128:
         return
     monkeypatch.delenv("MFA_BWDQ_BYTES")
