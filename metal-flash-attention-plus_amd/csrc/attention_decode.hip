@@ -1316,6 +1316,13 @@ constexpr int decode16_lds() {
   return ring > merge ? ring : merge;
 }
 
+// LDS of the 32-row kernels: the four waves' FP32 partials and their (m, l) (decode_finish32),
+// which the waves' tile rings (4 waves · 4 · 32 · DP bytes) fit in.
+template <int DP>
+constexpr int decode32_lds() {
+  return 4 * 2 * 2 * 32 * DP + 1024;
+}
+
 template <class E, int DP, int SRC>
 __global__ void __launch_bounds__(256, DP == 256 && SRC != SRC_I8 ? 1 : 2)
     mfa_fwd_decode16_kernel(DecodeParams dp) {
@@ -1958,12 +1965,33 @@ size_t decode_workspace_bytes(int B, int Hkv, int rows, int C, int D) {
 }
 
 // The merge pass: one row per wave, or with more than 32 partials (splits) per row one row per
-// workgroup (4 waves).
-static hipError_t launch_merge(const DecodeParams& dp, hipStream_t stream) {
+// workgroup (4 waves).  `e` is the forward launch's result; a fused forward needs no merge.
+static hipError_t launch_merge(hipError_t e, const DecodeParams& dp, hipStream_t stream) {
+  if (e != hipSuccess || dp.fused) return e;
   const int64_t nrows = (int64_t)dp.f.B * dp.f.H * dp.f.R;
   if (dp.nsplit > 32)
     return launch(mfa_decode_merge4_kernel, dim3((unsigned)nrows), dim3(256), 0, stream, dp);
   return launch(mfa_decode_merge_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, stream, dp);
+}
+
+// What both dispatchers derive from a call over C keys (p.C is ignored): in *dp the split layout
+// and the partials workspace carved up; returned, the grid and the padded head dimension.
+struct DecodeLaunch { hipError_t err; dim3 grid; int DP; };
+static DecodeLaunch decode_params(const FwdParams& p, int C, void* workspace, DecodeParams* dp) {
+  dp->f = p;
+  dp->f.C = C;
+  dp->rows = (p.H / p.Hkv) * p.R;
+  decode_layout(p.B, p.Hkv, dp->rows, C, &dp->nrt, &dp->nsplit, &dp->chunk);
+  const size_t parts = (size_t)p.B * p.Hkv * dp->nrt * dp->nsplit * 32;
+  dp->opart = (float*)workspace;
+  dp->mlpart = workspace ? (float2*)((char*)workspace + ((parts * p.D * 4 + 255) & ~(size_t)255))
+                         : nullptr;
+  dp->fused = decode_fused(dp->nsplit);
+  const int units = p.B * p.Hkv * dp->nrt;
+  const hipError_t err = units >= 65536               ? hipErrorNotSupported
+                         : !dp->fused && !workspace ? hipErrorInvalidValue
+                                                    : hipSuccess;
+  return {err, dim3(dp->nsplit, units, 1), p.D <= 64 ? 64 : p.D <= 128 ? 128 : 256};
 }
 
 hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hipStream_t stream) {
@@ -1972,21 +2000,11 @@ hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hi
   if (p.k.prec != p.v.prec || (p.k.prec != P_INT8 && !i4 && !kv16) || p.k.ss != p.v.ss)
     return hipErrorNotSupported;
   DecodeParams dp;
-  dp.f = p;
   // Causal (key <= query index): no row sees a key past R - 1.
-  if (p.mask.causal) dp.f.C = decode_keys(p.R, p.C, true);
-  dp.rows = (p.H / p.Hkv) * p.R;
-  decode_layout(p.B, p.Hkv, dp.rows, dp.f.C, &dp.nrt, &dp.nsplit, &dp.chunk);
-  const size_t parts = (size_t)p.B * p.Hkv * dp.nrt * dp.nsplit * 32;
-  dp.opart = (float*)workspace;
-  dp.mlpart = workspace ? (float2*)((char*)workspace + ((parts * p.D * 4 + 255) & ~(size_t)255))
-                        : nullptr;
-  const int units = p.B * p.Hkv * dp.nrt;
-  if (units >= 65536) return hipErrorNotSupported;
-  const dim3 grid(dp.nsplit, units, 1);
-  const int DP = p.D <= 64 ? 64 : p.D <= 128 ? 128 : 256;
-  dp.fused = decode_fused(dp.nsplit);
-  if (!dp.fused && !workspace) return hipErrorInvalidValue;
+  const DecodeLaunch dl = decode_params(p, decode_keys(p.R, p.C, p.mask.causal), workspace, &dp);
+  if (dl.err != hipSuccess) return dl.err;
+  const dim3 grid = dl.grid;
+  const int DP = dl.DP;
   hipError_t e = hipErrorNotSupported;
   // At most 16 rows per kv head: the 16x16x32 kernel (MFA_DECODE16=0: the 32-row one; =4: INT4
   // only; =2: not at D = 256, A/B switches).
@@ -2008,17 +2026,16 @@ hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hi
     MFA_DEC16(P_FP16, F16, 256)
     MFA_DEC16(P_BF16, BF16, 256)
 #undef MFA_DEC16
-    if (e != hipSuccess || dp.fused) return e;
-    return launch_merge(dp, stream);
+    return launch_merge(e, dp, stream);
   }
 #define MFA_DEC(ELEM, EE, DPV)                                                                 \
   if (elem == ELEM && DP == DPV)                                                               \
     e = kv16 ? launch(mfa_fwd_decode_kernel<EE, DPV, SRC_SAME>, grid, dim3(256),               \
-                      4 * 2 * 2 * 32 * DPV + 1024, stream, dp)                                 \
+                      decode32_lds<DPV>(), stream, dp)                                         \
         : i4 ? launch(mfa_fwd_decode_kernel<EE, DPV, SRC_I4>, grid, dim3(256),                 \
-                      4 * 2 * 2 * 32 * DPV + 1024, stream, dp)                                 \
+                      decode32_lds<DPV>(), stream, dp)                                         \
              : launch(mfa_fwd_decode_kernel<EE, DPV, SRC_I8>, grid, dim3(256),                 \
-                      4 * 2 * 2 * 32 * DPV + 1024, stream, dp);
+                      decode32_lds<DPV>(), stream, dp);
   MFA_DEC(P_FP16, F16, 64)
   MFA_DEC(P_FP16, F16, 128)
   MFA_DEC(P_FP16, F16, 256)
@@ -2026,37 +2043,25 @@ hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hi
   MFA_DEC(P_BF16, BF16, 128)
   MFA_DEC(P_BF16, BF16, 256)
 #undef MFA_DEC
-  if (e != hipSuccess || dp.fused) return e;
-  return launch_merge(dp, stream);
+  return launch_merge(e, dp, stream);
 }
 
 // The paged forms.  p.C is the host-side cap on every sequence's length: split layout, grid and
 // workspace follow it (the lengths are device values), p.k / p.v are the pools (16-bit in the
-// compute type, or per-tensor INT8).  The same grid, LDS sizes, partial indexing and merge
-// kernels as fwd_decode_dispatch.
+// compute type, or per-tensor INT8).
 hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int elem,
                                      void* workspace, hipStream_t stream) {
   const bool kv16 = p.k.prec == elem && (elem == P_FP16 || elem == P_BF16);
   if (p.k.prec != p.v.prec || (p.k.prec != P_INT8 && !kv16) || p.k.ss != p.v.ss)
     return hipErrorNotSupported;
   PagedDecodeParams pp;
-  DecodeParams& dp = pp.d;
-  dp.f = p;
   pp.pg = pg;
-  dp.rows = (p.H / p.Hkv) * p.R;
-  decode_layout(p.B, p.Hkv, dp.rows, p.C, &dp.nrt, &dp.nsplit, &dp.chunk);
-  const size_t parts = (size_t)p.B * p.Hkv * dp.nrt * dp.nsplit * 32;
-  dp.opart = (float*)workspace;
-  dp.mlpart = workspace ? (float2*)((char*)workspace + ((parts * p.D * 4 + 255) & ~(size_t)255))
-                        : nullptr;
-  const int units = p.B * p.Hkv * dp.nrt;
-  if (units >= 65536) return hipErrorNotSupported;
-  const dim3 grid(dp.nsplit, units, 1);
-  const int DP = p.D <= 64 ? 64 : p.D <= 128 ? 128 : 256;
-  dp.fused = decode_fused(dp.nsplit);
-  if (!dp.fused && !workspace) return hipErrorInvalidValue;
+  const DecodeLaunch dl = decode_params(p, p.C, workspace, &pp.d);
+  if (dl.err != hipSuccess) return dl.err;
+  const dim3 grid = dl.grid;
+  const int DP = dl.DP;
   hipError_t e = hipErrorNotSupported;
-  const bool rows16 = dp.rows <= 16;
+  const bool rows16 = pp.d.rows <= 16;
 #define MFA_DECP(ELEM, EE, DPV)                                                                \
   if (elem == ELEM && DP == DPV) {                                                             \
     if (rows16)                                                                                \
@@ -2066,9 +2071,9 @@ hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int 
                         decode16_lds<DPV, SRC_I8>(), stream, pp);                              \
     else                                                                                       \
       e = kv16 ? launch(mfa_fwd_decode_paged_kernel<EE, DPV, SRC_SAME>, grid, dim3(256),       \
-                        4 * 2 * 2 * 32 * DPV + 1024, stream, pp)                               \
+                        decode32_lds<DPV>(), stream, pp)                                       \
                : launch(mfa_fwd_decode_paged_kernel<EE, DPV, SRC_I8>, grid, dim3(256),         \
-                        4 * 2 * 2 * 32 * DPV + 1024, stream, pp);                              \
+                        decode32_lds<DPV>(), stream, pp);                                      \
   }
   MFA_DECP(P_FP16, F16, 64)
   MFA_DECP(P_FP16, F16, 128)
@@ -2077,8 +2082,8 @@ hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int 
   MFA_DECP(P_BF16, BF16, 128)
   MFA_DECP(P_BF16, BF16, 256)
 #undef MFA_DECP
-  if (e != hipSuccess || dp.fused) return e;
-  return launch_merge(dp, stream);
+  return launch_merge(e, pp.d, stream);
 }
 
 }  // namespace mfa
+

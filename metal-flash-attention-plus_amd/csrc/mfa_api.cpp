@@ -1839,12 +1839,146 @@ extern "C" mfa_status_t mfa_mla_forward_absorbed(const mfa_mla_descriptor_t* des
 }
 
 // =========================================================================================
-// Paged, ragged KV-cache decode (no reference counterpart): the split-KV decode kernels over a
-// block-table cache (attention_decode.hip, the *_paged_kernel entry points).  Sequence lengths
-// and the block table are device values the host never reads: the split layout, the grid and the
-// partials workspace (library scratch slot 15) follow max_seq_len.
+// The paged, ragged KV cache (no reference counterpart): decode, append and prefill over one
+// cache struct.  Sequence lengths and the block table are device values the host never reads,
+// and no kernel checks the table or the strides again: the view below is the only guard.
 namespace {
 
+// A checked mfa_paged_kv_cache_t.  The rules, the same for every entry point:
+//  - the page size is a power of two >= 32 (pages hold whole 32-key tiles);
+//  - the pools are FP16 / BF16 of the caller's 16-bit operand or, where the entry point takes
+//    them, INT8 (INT4 pools — 64-key tiles in the 16-row kernel, packed rows — are left for a
+//    later change);
+//  - D is a multiple of 8 (INT8: 16), at most 256; INT8 zero points lie in [-128, 128];
+//  - the three strides are non-negative multiples of 16 bytes, the token stride at least D and
+//    below 2^24 bytes (row offsets inside a 32-key tile are 32-bit buffer offsets);
+//  - no sequence is longer than 2^30 keys, and the block table is indexed with 32 bits.
+struct PagedCacheView {
+  int cprec;
+  bool i8;
+  int es;          // bytes per element
+  int64_t cap;     // min(max_seq_len, max_pages_per_seq · page_size): the bound on every length
+  mfa::PagedKv pg;
+};
+
+// Everything that needs no buffer.  prec16 is the caller's 16-bit operand precision and `whose`
+// the word its message uses for it ("query's", "input's").
+mfa_status_t paged_cache_view(const char* what, const mfa_paged_kv_cache_t& c, int64_t B, int64_t D,
+                              uint32_t max_seq_len, int prec16, const char* whose, bool allow_i8,
+                              PagedCacheView* v) {
+  const uint32_t ps = c.page_size;
+  if (ps < 32 || (ps & (ps - 1)) != 0)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: page size %u is not a power of two >= 32", what, ps);
+  const int cprec = c.precision;
+  if (!allow_i8 && (cprec == MFA_PRECISION_INT8 || cprec == MFA_PRECISION_INT4))
+    return fail(MFA_ERR_UNSUPPORTED,
+                "%s: quantised pools (precision %d) are not supported; 16-bit pools only", what,
+                cprec);
+  const bool i8 = cprec == MFA_PRECISION_INT8;
+  if (!i8 && cprec != MFA_PRECISION_FP16 && cprec != MFA_PRECISION_BF16)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: cache precision %d (%s)", what, cprec,
+                allow_i8 ? "FP16, BF16 or INT8" : "FP16 or BF16");
+  if (!i8 && cprec != prec16)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: %scache precision %d differs from the %s %d", what,
+                allow_i8 ? "16-bit " : "", cprec, whose, prec16);
+  if (D % (i8 ? 16 : 8) != 0 || D > 256)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of %d, at most 256)",
+                what, (long long)D, i8 ? 16 : 8);
+  if (i8 && (c.k_zero_point < -128 || c.k_zero_point > 128 || c.v_zero_point < -128 ||
+             c.v_zero_point > 128))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: zero point outside [-128, 128]", what);
+  const int es = i8 ? 1 : 2;
+  for (int i = 0; i < 3; ++i)
+    if (c.strides[i] < 0 || (c.strides[i] * es) % 16 != 0)
+      return fail(MFA_ERR_UNSUPPORTED, "%s: cache stride %d is not a multiple of 16 bytes", what, i);
+  if (c.strides[2] < D || c.strides[2] * es >= ((int64_t)1 << 24))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: token stride %lld", what, (long long)c.strides[2]);
+  const int64_t cap = std::min<int64_t>(max_seq_len, (int64_t)c.max_pages_per_seq * ps);
+  if (cap > ((int64_t)1 << 30))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: more than 2^30 keys per sequence", what);
+  if ((int64_t)c.max_pages_per_seq * B >= ((int64_t)1 << 31) || c.num_pages > 0x7fffffffu)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: block table too large", what);
+  memset(v, 0, sizeof(*v));
+  v->cprec = cprec; v->i8 = i8; v->es = es; v->cap = cap;
+  v->pg.block_table = c.block_table;
+  v->pg.seq_lens = c.seq_lens;
+  v->pg.page_bytes = c.strides[0] * es;
+  v->pg.head_bytes = c.strides[1] * es;
+  v->pg.lg_page = __builtin_ctz(ps);
+  v->pg.max_pages = (int)c.max_pages_per_seq;
+  v->pg.num_pages = (int)c.num_pages;
+  return MFA_SUCCESS;
+}
+
+// After the caller's empty-call success (an empty call may pass null buffers): the caller's own
+// buffers (`own` names them, have_own says they are there), the cache's four, the pools' alignment.
+mfa_status_t paged_cache_buffers(const char* what, const mfa_paged_kv_cache_t& c, const char* own,
+                                 bool have_own) {
+  if (!have_own || !c.k_pool || !c.v_pool || !c.block_table || !c.seq_lens)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "%s requires %s, both pools, block_table and seq_lens",
+                what, own);
+  if (!aligned16(c.k_pool) || !aligned16(c.v_pool))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: pools must be 16-byte aligned", what);
+  return MFA_SUCCESS;
+}
+
+// The pools as the K / V operands of a forward: only ptr, the token stride, precision and zero
+// point are read.
+void paged_pool_operands(const mfa_paged_kv_cache_t& c, const PagedCacheView& v, int D,
+                         mfa::FwdParams* p) {
+  for (mfa::Operand* op : {&p->k, &p->v}) {
+    const bool k = op == &p->k;
+    op->ptr = k ? c.k_pool : c.v_pool;
+    op->ss = c.strides[2];
+    op->sd = 1;
+    op->prec = v.cprec;
+    op->vec = 1;
+    op->scale = 1.f;
+    op->zp = v.i8 ? (k ? c.k_zero_point : c.v_zero_point) : 0;
+    op->cols = D;
+  }
+}
+
+// The caller's logsumexp, or FP32 scratch for n values when it passes none.
+mfa_status_t l_or_scratch(void* logsumexp, int64_t n, hipStream_t stream, void** l) {
+  *l = logsumexp;
+  if (logsumexp) return MFA_SUCCESS;
+  if (mfa::plan_capture()) {
+    *l = (void*)kPlanDummy;
+    return MFA_SUCCESS;
+  }
+  return scratch((size_t)n * 4, l, 0, stream);
+}
+
+// A plan query: `run` is the entry point with launches recorded, on the given cache with its null
+// pointers replaced or, without one, on a dense 16-bit cache of 256-key pages in `prec16`.
+template <class Desc, class Run>
+mfa_status_t paged_plan(const Desc& d, int prec16, const mfa_paged_kv_cache_t* cache,
+                        mfa_kernel_plan_t* out, Run run) {
+  memset(out, 0, sizeof(*out));
+  mfa_paged_kv_cache_t c;
+  if (cache) {
+    c = *cache;
+  } else {
+    memset(&c, 0, sizeof(c));
+    c.precision = prec16;
+    c.k_scale = c.v_scale = 1.f;
+    c.page_size = 256;
+    c.max_pages_per_seq = (d.max_seq_len + 255) / 256;
+    c.num_pages = std::max<uint32_t>(1, c.max_pages_per_seq * d.batch_size);
+    c.strides[2] = d.head_dim;
+    c.strides[1] = (int64_t)c.page_size * d.head_dim;
+    c.strides[0] = c.strides[1] * d.num_kv_heads;
+  }
+  fill_dummy(c.k_pool); fill_dummy(c.v_pool); fill_dummy(c.block_table); fill_dummy(c.seq_lens);
+  CaptureScope scope;
+  const mfa_status_t st = run(c);
+  if (st == MFA_SUCCESS) scope.copy_to(out);
+  return st;
+}
+
+// Split-KV decode over the cache (attention_decode.hip, the *_paged_kernel entry points).  The
+// split layout, the grid and the partials workspace (library scratch slot 15) follow max_seq_len.
 mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void* query,
                           const int64_t* query_strides, const mfa_paged_kv_cache_t* cache,
                           float* output, void* logsumexp, hipStream_t stream) {
@@ -1859,161 +1993,63 @@ mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void*
   if (H % Hkv != 0)
     return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: %lld heads over %lld kv heads", what,
                 (long long)H, (long long)Hkv);
-  const uint32_t ps = cache->page_size;
-  if (ps < 32 || (ps & (ps - 1)) != 0)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: page size %u is not a power of two >= 32", what, ps);
   const int qprec = resolve_precisions(base).mem[MFA_OPERAND_Q];
   const int elem = elem_of(qprec);
   if (elem != 1 && elem != 2)
     return fail(MFA_ERR_UNSUPPORTED, "%s: query precision %d (FP16 or BF16)", what, qprec);
-  const int cprec = cache->precision;
-  // INT4 pools (64-key tiles in the 16-row kernel, packed rows) are left for a later change.
-  if (cprec != MFA_PRECISION_INT8 && cprec != MFA_PRECISION_FP16 && cprec != MFA_PRECISION_BF16)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: cache precision %d (FP16, BF16 or INT8)", what, cprec);
-  const bool i8 = cprec == MFA_PRECISION_INT8;
-  if (!i8 && cprec != qprec)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: 16-bit cache precision %d differs from the query's %d",
-                what, cprec, qprec);
-  if (D % (i8 ? 16 : 8) != 0 || D > 256)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of %d, at most 256)",
-                what, (long long)D, i8 ? 16 : 8);
+  PagedCacheView cv;
+  mfa_status_t st =
+      paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", true, &cv);
+  if (st != MFA_SUCCESS) return st;
   if (base.has_sparse_mask || (base.sparsity_pattern != MFA_SPARSITY_NONE &&
                                base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
     return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);
-  mfa_status_t st = check_transposes(base, false, what);
-  if (st != MFA_SUCCESS) return st;
+  if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
   const float scale = resolve_scale(base, (int)D);
-  const float fk = i8 ? cache->k_scale : 1.f, fv = i8 ? cache->v_scale : 1.f;
+  const float fk = cv.i8 ? cache->k_scale : 1.f, fv = cv.i8 ? cache->v_scale : 1.f;
   if (!(scale > 0.f) || !(fk > 0.f) || !(1.442695041f * scale * fk > 0.f))
     return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
-  if (i8 && (cache->k_zero_point < -128 || cache->k_zero_point > 128 ||
-             cache->v_zero_point < -128 || cache->v_zero_point > 128))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: zero point outside [-128, 128]", what);
-  const int es = i8 ? 1 : 2;
-  for (int i = 0; i < 3; ++i)
-    if (cache->strides[i] < 0 || (cache->strides[i] * es) % 16 != 0)
-      return fail(MFA_ERR_UNSUPPORTED, "%s: cache stride %d is not a multiple of 16 bytes", what, i);
-  // Row offsets inside a 32-key tile are 32-bit buffer offsets.
-  if (cache->strides[2] < D || cache->strides[2] * es >= ((int64_t)1 << 24))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: token stride %lld", what, (long long)cache->strides[2]);
   const int64_t rows = (H / Hkv) * R;
   if (B * Hkv * ((rows + 31) / 32) >= 65536)
     return fail(MFA_ERR_UNSUPPORTED, "%s: %lld x %lld x %lld units exceed the grid", what,
                 (long long)B, (long long)Hkv, (long long)((rows + 31) / 32));
   if (B * H * R >= ((int64_t)1 << 31))
     return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
-  const int64_t cap = std::min<int64_t>(desc->max_seq_len, (int64_t)cache->max_pages_per_seq * ps);
-  if (cap > ((int64_t)1 << 30))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: more than 2^30 keys per sequence", what);
-  if ((int64_t)cache->max_pages_per_seq * B >= ((int64_t)1 << 31) || cache->num_pages > 0x7fffffffu)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: block table too large", what);
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
-  if (!query || !output || !cache->k_pool || !cache->v_pool || !cache->block_table ||
-      !cache->seq_lens)
-    return fail(MFA_ERR_INVALID_ARGUMENT,
-                "%s requires query, output, both pools, block_table and seq_lens", what);
-  if (!aligned16(cache->k_pool) || !aligned16(cache->v_pool))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: pools must be 16-byte aligned", what);
+  if ((st = paged_cache_buffers(what, *cache, "query, output", query && output)) != MFA_SUCCESS)
+    return st;
 
   mfa::FwdParams p;
   memset(&p, 0, sizeof(p));
   p.q = make_operand(query, qprec, (int)B, (int)H, (int)R, (int)D, query_strides, 0);
   if (p.q.sd != 1 || !p.q.vec)
     return fail(MFA_ERR_UNSUPPORTED, "%s: query rows must be dense and 16-byte aligned", what);
-  // The pools as operands: only ptr, the token stride, precision and zero point are read.
-  for (mfa::Operand* op : {&p.k, &p.v}) {
-    const bool k = op == &p.k;
-    op->ptr = k ? cache->k_pool : cache->v_pool;
-    op->ss = cache->strides[2];
-    op->sd = 1;
-    op->prec = cprec;
-    op->vec = 1;
-    op->scale = 1.f;
-    op->zp = i8 ? (k ? cache->k_zero_point : cache->v_zero_point) : 0;
-    op->cols = (int)D;
-  }
+  paged_pool_operands(*cache, cv, (int)D, &p);
   p.o = output;
   out_strides((int)R, (int)D, false, &p.o_ss, &p.o_sd);
   p.o_sh = R * D;
   p.o_sb = H * R * D;
   p.l_f16 = resolve_precisions(base).mem[MFA_OPERAND_L] == MFA_PRECISION_FP16;
-  void* L = logsumexp;
-  if (!L) {
-    if (mfa::plan_capture()) L = (void*)kPlanDummy;
-    else if ((st = scratch((size_t)(B * H * R) * 4, &L, 0, stream)) != MFA_SUCCESS) return st;
-  }
-  p.l = L;
+  if ((st = l_or_scratch(logsumexp, B * H * R, stream, &p.l)) != MFA_SUCCESS) return st;
   p.B = (int)B; p.H = (int)H; p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
-  p.C = (int)cap;
+  p.C = (int)cv.cap;
   p.c_log2 = 1.442695041f * scale * fk;
   p.o_mul = fv;
   p.mask.causal = base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
   p.mask.skip_ok = 1;
 
-  mfa::PagedKv pg;
-  memset(&pg, 0, sizeof(pg));
-  pg.block_table = cache->block_table;
-  pg.seq_lens = cache->seq_lens;
-  pg.page_bytes = cache->strides[0] * es;
-  pg.head_bytes = cache->strides[1] * es;
-  pg.lg_page = __builtin_ctz(ps);
-  pg.max_pages = (int)cache->max_pages_per_seq;
-  pg.num_pages = (int)cache->num_pages;
-
   void* ws = nullptr;
-  const size_t wsb = mfa::decode_workspace_bytes((int)B, (int)Hkv, (int)rows, (int)cap, (int)D);
+  const size_t wsb = mfa::decode_workspace_bytes((int)B, (int)Hkv, (int)rows, (int)cv.cap, (int)D);
   if (wsb && mfa::plan_capture()) ws = (void*)kPlanDummy;
   else if (wsb && (st = scratch(wsb, &ws, 15, stream)) != MFA_SUCCESS) return st;
-  const hipError_t e = mfa::fwd_decode_paged_dispatch(p, pg, elem, ws, stream);
+  const hipError_t e = mfa::fwd_decode_paged_dispatch(p, cv.pg, elem, ws, stream);
   if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
   return hip_status(e, "mfa_fwd (paged decode) launch");
 }
 
-}  // namespace
-
-extern "C" mfa_status_t mfa_paged_decode_forward(const mfa_paged_decode_descriptor_t* desc,
-                                                 const void* query, const int64_t* query_strides,
-                                                 const mfa_paged_kv_cache_t* cache, float* output,
-                                                 void* logsumexp, void* stream) {
-  return paged_decode(desc, query, query_strides, cache, output, logsumexp, (hipStream_t)stream);
-}
-
-extern "C" mfa_status_t mfa_paged_decode_plan(const mfa_paged_decode_descriptor_t* desc,
-                                              const mfa_paged_kv_cache_t* cache,
-                                              mfa_kernel_plan_t* out) {
-  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  memset(out, 0, sizeof(*out));
-  mfa_paged_kv_cache_t c;
-  if (cache) {
-    c = *cache;
-  } else {
-    // A dense 16-bit cache in the query's type, 256-key pages.
-    memset(&c, 0, sizeof(c));
-    c.precision = resolve_precisions(desc->base).mem[MFA_OPERAND_Q];
-    c.k_scale = c.v_scale = 1.f;
-    c.page_size = 256;
-    c.max_pages_per_seq = (desc->max_seq_len + 255) / 256;
-    c.num_pages = std::max<uint32_t>(1, c.max_pages_per_seq * desc->batch_size);
-    c.strides[2] = desc->head_dim;
-    c.strides[1] = (int64_t)c.page_size * desc->head_dim;
-    c.strides[0] = c.strides[1] * desc->num_kv_heads;
-  }
-  fill_dummy(c.k_pool); fill_dummy(c.v_pool); fill_dummy(c.block_table); fill_dummy(c.seq_lens);
-  CaptureScope scope;
-  const mfa_status_t st = paged_decode(desc, (const void*)kPlanDummy, nullptr, &c,
-                                       (float*)kPlanDummy, nullptr, nullptr);
-  if (st == MFA_SUCCESS) scope.copy_to(out);
-  return st;
-}
-
-// =========================================================================================
-// The write side of the paged cache (paged_append.hip): new key / value rows to their slots in
-// the pools, addressed on the device from seq_lens (the lengths after the append), new_lens and
-// the block table.  One launch, no scratch, nothing read on the host.  The cache struct is
-// checked by paged_decode's rules, restated here (that function's checks are interleaved with
-// the query's and keep their messages).
-namespace {
-
+// The write side (paged_append.hip): new key / value rows to their slots in the pools, addressed
+// on the device from seq_lens (the lengths after the append), new_lens and the block table.  One
+// launch, no scratch, nothing read on the host.
 mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void* key,
                           const void* value, const int64_t* key_strides,
                           const int64_t* value_strides, const int32_t* new_lens,
@@ -2025,50 +2061,23 @@ mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void*
   if (Hkv == 0 || D == 0 || desc->max_seq_len == 0 || cache->max_pages_per_seq == 0 ||
       cache->num_pages == 0)
     return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: empty shape", what);
-  const uint32_t ps = cache->page_size;
-  if (ps < 32 || (ps & (ps - 1)) != 0)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: page size %u is not a power of two >= 32", what, ps);
   const int iprec = desc->input_precision;
   if (iprec != MFA_PRECISION_FP16 && iprec != MFA_PRECISION_BF16)
     return fail(MFA_ERR_UNSUPPORTED, "%s: input precision %d (FP16 or BF16)", what, iprec);
-  const int cprec = cache->precision;
-  if (cprec != MFA_PRECISION_INT8 && cprec != MFA_PRECISION_FP16 && cprec != MFA_PRECISION_BF16)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: cache precision %d (FP16, BF16 or INT8)", what, cprec);
-  const bool i8 = cprec == MFA_PRECISION_INT8;
-  if (!i8 && cprec != iprec)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: 16-bit cache precision %d differs from the input's %d",
-                what, cprec, iprec);
-  if (D % (i8 ? 16 : 8) != 0 || D > 256)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of %d, at most 256)",
-                what, (long long)D, i8 ? 16 : 8);
-  if (i8) {
+  PagedCacheView cv;
+  mfa_status_t st =
+      paged_cache_view(what, *cache, B, D, desc->max_seq_len, iprec, "input's", true, &cv);
+  if (st != MFA_SUCCESS) return st;
+  // The kernel divides by the scales: stricter than the readers' rule.
+  if (cv.i8)
     for (const float s : {cache->k_scale, cache->v_scale})
       if (!(s > 0.f) || !std::isfinite(s))
         return fail(MFA_ERR_UNSUPPORTED, "%s: scale %g is not finite and positive", what, (double)s);
-    if (cache->k_zero_point < -128 || cache->k_zero_point > 128 || cache->v_zero_point < -128 ||
-        cache->v_zero_point > 128)
-      return fail(MFA_ERR_UNSUPPORTED, "%s: zero point outside [-128, 128]", what);
-  }
-  const int es = i8 ? 1 : 2;
-  for (int i = 0; i < 3; ++i)
-    if (cache->strides[i] < 0 || (cache->strides[i] * es) % 16 != 0)
-      return fail(MFA_ERR_UNSUPPORTED, "%s: cache stride %d is not a multiple of 16 bytes", what, i);
-  if (cache->strides[2] < D || cache->strides[2] * es >= ((int64_t)1 << 24))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: token stride %lld", what, (long long)cache->strides[2]);
   if (B * R >= ((int64_t)1 << 31))
     return fail(MFA_ERR_UNSUPPORTED, "%s: too many rows", what);
-  const int64_t cap = std::min<int64_t>(desc->max_seq_len, (int64_t)cache->max_pages_per_seq * ps);
-  if (cap > ((int64_t)1 << 30))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: more than 2^30 keys per sequence", what);
-  if ((int64_t)cache->max_pages_per_seq * B >= ((int64_t)1 << 31) || cache->num_pages > 0x7fffffffu)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: block table too large", what);
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to write; the buffers may be null
-  if (!key || !value || !cache->k_pool || !cache->v_pool || !cache->block_table ||
-      !cache->seq_lens)
-    return fail(MFA_ERR_INVALID_ARGUMENT,
-                "%s requires key, value, both pools, block_table and seq_lens", what);
-  if (!aligned16(cache->k_pool) || !aligned16(cache->v_pool))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: pools must be 16-byte aligned", what);
+  if ((st = paged_cache_buffers(what, *cache, "key, value", key && value)) != MFA_SUCCESS)
+    return st;
 
   mfa::PagedAppendParams p;
   memset(&p, 0, sizeof(p));
@@ -2087,71 +2096,22 @@ mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void*
     p.src[i] = src;
     p.s_sb[i] = s[0] * 2; p.s_sh[i] = s[1] * 2; p.s_ss[i] = s[2] * 2;
     p.pool[i] = const_cast<void*>(i ? cache->v_pool : cache->k_pool);
-    p.scale[i] = i8 ? (i ? cache->v_scale : cache->k_scale) : 1.f;
-    p.zp[i] = i8 ? (i ? cache->v_zero_point : cache->k_zero_point) : 0;
+    p.scale[i] = cv.i8 ? (i ? cache->v_scale : cache->k_scale) : 1.f;
+    p.zp[i] = cv.i8 ? (i ? cache->v_zero_point : cache->k_zero_point) : 0;
   }
-  p.pg.block_table = cache->block_table;
-  p.pg.seq_lens = cache->seq_lens;
-  p.pg.page_bytes = cache->strides[0] * es;
-  p.pg.head_bytes = cache->strides[1] * es;
-  p.pg.lg_page = __builtin_ctz(ps);
-  p.pg.max_pages = (int)cache->max_pages_per_seq;
-  p.pg.num_pages = (int)cache->num_pages;
+  p.pg = cv.pg;
   p.new_lens = new_lens;
-  p.tok_bytes = cache->strides[2] * es;
+  p.tok_bytes = cache->strides[2] * cv.es;
   p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
-  p.cap = (int)cap;
+  p.cap = (int)cv.cap;
   p.rows_total = (int)(B * R);
-  return hip_status(mfa::paged_append_dispatch(p, iprec, i8, stream), "mfa_paged_kv_append launch");
+  return hip_status(mfa::paged_append_dispatch(p, iprec, cv.i8, stream),
+                    "mfa_paged_kv_append launch");
 }
 
-}  // namespace
-
-extern "C" mfa_status_t mfa_paged_kv_append(const mfa_paged_append_descriptor_t* desc,
-                                            const void* key, const void* value,
-                                            const int64_t* key_strides,
-                                            const int64_t* value_strides, const int32_t* new_lens,
-                                            const mfa_paged_kv_cache_t* cache, void* stream) {
-  return paged_append(desc, key, value, key_strides, value_strides, new_lens, cache,
-                      (hipStream_t)stream);
-}
-
-extern "C" mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descriptor_t* desc,
-                                                 const mfa_paged_kv_cache_t* cache,
-                                                 mfa_kernel_plan_t* out) {
-  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  memset(out, 0, sizeof(*out));
-  mfa_paged_kv_cache_t c;
-  if (cache) {
-    c = *cache;
-  } else {
-    // A dense 16-bit cache in the input's type, 256-key pages.
-    memset(&c, 0, sizeof(c));
-    c.precision = desc->input_precision;
-    c.k_scale = c.v_scale = 1.f;
-    c.page_size = 256;
-    c.max_pages_per_seq = (desc->max_seq_len + 255) / 256;
-    c.num_pages = std::max<uint32_t>(1, c.max_pages_per_seq * desc->batch_size);
-    c.strides[2] = desc->head_dim;
-    c.strides[1] = (int64_t)c.page_size * desc->head_dim;
-    c.strides[0] = c.strides[1] * desc->num_kv_heads;
-  }
-  fill_dummy(c.k_pool); fill_dummy(c.v_pool); fill_dummy(c.block_table); fill_dummy(c.seq_lens);
-  CaptureScope scope;
-  const mfa_status_t st = paged_append(desc, (const void*)kPlanDummy, (const void*)kPlanDummy,
-                                       nullptr, nullptr, nullptr, &c, nullptr);
-  if (st == MFA_SUCCESS) scope.copy_to(out);
-  return st;
-}
-
-// =========================================================================================
 // Paged prefill (attention_prefill_paged.hip): the R rows of each sequence in `query` — a prompt
-// or a chunk of one, ragged through new_lens — attend to the paged cache they were appended to.
-// One launch of 128-row query blocks, no workspace but the scratch L; lengths, row counts and the
-// block table are device values the host never reads.  The cache struct is checked by
-// paged_decode's rules, restated here with this call's messages; pools are 16-bit only.
-namespace {
-
+// or a chunk of one, ragged through new_lens — attend to the cache they were appended to.  One
+// launch of 128-row query blocks, no workspace but the scratch L; 16-bit pools only.
 mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const void* query,
                            const int64_t* query_strides, const int32_t* new_lens,
                            const mfa_paged_kv_cache_t* cache, float* output, void* logsumexp,
@@ -2167,106 +2127,91 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
   if (H % Hkv != 0)
     return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: %lld heads over %lld kv heads", what,
                 (long long)H, (long long)Hkv);
-  const uint32_t ps = cache->page_size;
-  if (ps < 32 || (ps & (ps - 1)) != 0)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: page size %u is not a power of two >= 32", what, ps);
   const int qprec = resolve_precisions(base).mem[MFA_OPERAND_Q];
   const int elem = elem_of(qprec);
   if (elem != 1 && elem != 2)
     return fail(MFA_ERR_UNSUPPORTED, "%s: query precision %d (FP16 or BF16)", what, qprec);
-  const int cprec = cache->precision;
-  if (cprec == MFA_PRECISION_INT8 || cprec == MFA_PRECISION_INT4)
-    return fail(MFA_ERR_UNSUPPORTED,
-                "%s: quantised pools (precision %d) are not supported; 16-bit pools only", what,
-                cprec);
-  if (cprec != MFA_PRECISION_FP16 && cprec != MFA_PRECISION_BF16)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: cache precision %d (FP16 or BF16)", what, cprec);
-  if (cprec != qprec)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: cache precision %d differs from the query's %d", what,
-                cprec, qprec);
-  if (D % 8 != 0 || D > 256)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of 8, at most 256)",
-                what, (long long)D);
+  PagedCacheView cv;
+  mfa_status_t st =
+      paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", false, &cv);
+  if (st != MFA_SUCCESS) return st;
   if (base.has_sparse_mask || (base.sparsity_pattern != MFA_SPARSITY_NONE &&
                                base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
     return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);
-  mfa_status_t st = check_transposes(base, false, what);
-  if (st != MFA_SUCCESS) return st;
+  if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
   const float scale = resolve_scale(base, (int)D);
   if (!(scale > 0.f) || !(1.442695041f * scale > 0.f))
     return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
-  for (int i = 0; i < 3; ++i)
-    if (cache->strides[i] < 0 || (cache->strides[i] * 2) % 16 != 0)
-      return fail(MFA_ERR_UNSUPPORTED, "%s: cache stride %d is not a multiple of 16 bytes", what, i);
-  // Row offsets inside a 32-key segment are 32-bit buffer offsets.
-  if (cache->strides[2] < D || cache->strides[2] * 2 >= ((int64_t)1 << 24))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: token stride %lld", what, (long long)cache->strides[2]);
   if (B * H * R >= ((int64_t)1 << 31))
     return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
   if (B * H * ((R + 127) / 128) >= ((int64_t)1 << 31))
     return fail(MFA_ERR_UNSUPPORTED, "%s: the query blocks exceed the grid", what);
-  const int64_t cap = std::min<int64_t>(desc->max_seq_len, (int64_t)cache->max_pages_per_seq * ps);
-  if (cap > ((int64_t)1 << 30))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: more than 2^30 keys per sequence", what);
-  if ((int64_t)cache->max_pages_per_seq * B >= ((int64_t)1 << 31) || cache->num_pages > 0x7fffffffu)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: block table too large", what);
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
-  if (!query || !output || !cache->k_pool || !cache->v_pool || !cache->block_table ||
-      !cache->seq_lens)
-    return fail(MFA_ERR_INVALID_ARGUMENT,
-                "%s requires query, output, both pools, block_table and seq_lens", what);
-  if (!aligned16(cache->k_pool) || !aligned16(cache->v_pool))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: pools must be 16-byte aligned", what);
+  if ((st = paged_cache_buffers(what, *cache, "query, output", query && output)) != MFA_SUCCESS)
+    return st;
 
   mfa::FwdParams p;
   memset(&p, 0, sizeof(p));
   p.q = make_operand(query, qprec, (int)B, (int)H, (int)R, (int)D, query_strides, 0);
   if (p.q.sd != 1 || !p.q.vec)
     return fail(MFA_ERR_UNSUPPORTED, "%s: query rows must be dense and 16-byte aligned", what);
-  // The pools as operands: only ptr, the token stride and the precision are read.
-  for (mfa::Operand* op : {&p.k, &p.v}) {
-    op->ptr = op == &p.k ? cache->k_pool : cache->v_pool;
-    op->ss = cache->strides[2];
-    op->sd = 1;
-    op->prec = cprec;
-    op->vec = 1;
-    op->scale = 1.f;
-    op->cols = (int)D;
-  }
+  paged_pool_operands(*cache, cv, (int)D, &p);
   p.o = output;
   out_strides((int)R, (int)D, false, &p.o_ss, &p.o_sd);
   p.o_sh = R * D;
   p.o_sb = H * R * D;
   p.l_f16 = resolve_precisions(base).mem[MFA_OPERAND_L] == MFA_PRECISION_FP16;
-  void* L = logsumexp;
-  if (!L) {
-    if (mfa::plan_capture()) L = (void*)kPlanDummy;
-    else if ((st = scratch((size_t)(B * H * R) * 4, &L, 0, stream)) != MFA_SUCCESS) return st;
-  }
-  p.l = L;
+  if ((st = l_or_scratch(logsumexp, B * H * R, stream, &p.l)) != MFA_SUCCESS) return st;
   p.B = (int)B; p.H = (int)H; p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
-  p.C = (int)cap;
+  p.C = (int)cv.cap;
   p.c_log2 = 1.442695041f * scale;
   p.o_mul = 1.f;
   p.mask.causal = base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
   p.mask.skip_ok = 1;
 
-  mfa::PagedKv pg;
-  memset(&pg, 0, sizeof(pg));
-  pg.block_table = cache->block_table;
-  pg.seq_lens = cache->seq_lens;
-  pg.page_bytes = cache->strides[0] * 2;
-  pg.head_bytes = cache->strides[1] * 2;
-  pg.lg_page = __builtin_ctz(ps);
-  pg.max_pages = (int)cache->max_pages_per_seq;
-  pg.num_pages = (int)cache->num_pages;
-
-  const hipError_t e = mfa::fwd_prefill_paged_dispatch(p, pg, new_lens, elem, stream);
+  const hipError_t e = mfa::fwd_prefill_paged_dispatch(p, cv.pg, new_lens, elem, stream);
   if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
   return hip_status(e, "mfa_fwd (paged prefill) launch");
 }
 
 }  // namespace
+
+extern "C" mfa_status_t mfa_paged_decode_forward(const mfa_paged_decode_descriptor_t* desc,
+                                                 const void* query, const int64_t* query_strides,
+                                                 const mfa_paged_kv_cache_t* cache, float* output,
+                                                 void* logsumexp, void* stream) {
+  return paged_decode(desc, query, query_strides, cache, output, logsumexp, (hipStream_t)stream);
+}
+
+extern "C" mfa_status_t mfa_paged_decode_plan(const mfa_paged_decode_descriptor_t* desc,
+                                              const mfa_paged_kv_cache_t* cache,
+                                              mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return paged_plan(*desc, resolve_precisions(desc->base).mem[MFA_OPERAND_Q], cache, out,
+                    [&](const mfa_paged_kv_cache_t& c) {
+                      return paged_decode(desc, (const void*)kPlanDummy, nullptr, &c,
+                                          (float*)kPlanDummy, nullptr, nullptr);
+                    });
+}
+
+extern "C" mfa_status_t mfa_paged_kv_append(const mfa_paged_append_descriptor_t* desc,
+                                            const void* key, const void* value,
+                                            const int64_t* key_strides,
+                                            const int64_t* value_strides, const int32_t* new_lens,
+                                            const mfa_paged_kv_cache_t* cache, void* stream) {
+  return paged_append(desc, key, value, key_strides, value_strides, new_lens, cache,
+                      (hipStream_t)stream);
+}
+
+extern "C" mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descriptor_t* desc,
+                                                 const mfa_paged_kv_cache_t* cache,
+                                                 mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return paged_plan(*desc, desc->input_precision, cache, out, [&](const mfa_paged_kv_cache_t& c) {
+    return paged_append(desc, (const void*)kPlanDummy, (const void*)kPlanDummy, nullptr, nullptr,
+                        nullptr, &c, nullptr);
+  });
+}
 
 extern "C" mfa_status_t mfa_paged_prefill_forward(const mfa_paged_prefill_descriptor_t* desc,
                                                   const void* query, const int64_t* query_strides,
@@ -2281,26 +2226,10 @@ extern "C" mfa_status_t mfa_paged_prefill_plan(const mfa_paged_prefill_descripto
                                                const mfa_paged_kv_cache_t* cache,
                                                mfa_kernel_plan_t* out) {
   if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
-  memset(out, 0, sizeof(*out));
-  mfa_paged_kv_cache_t c;
-  if (cache) {
-    c = *cache;
-  } else {
-    // A dense 16-bit cache in the query's type, 256-key pages.
-    memset(&c, 0, sizeof(c));
-    c.precision = resolve_precisions(desc->base).mem[MFA_OPERAND_Q];
-    c.k_scale = c.v_scale = 1.f;
-    c.page_size = 256;
-    c.max_pages_per_seq = (desc->max_seq_len + 255) / 256;
-    c.num_pages = std::max<uint32_t>(1, c.max_pages_per_seq * desc->batch_size);
-    c.strides[2] = desc->head_dim;
-    c.strides[1] = (int64_t)c.page_size * desc->head_dim;
-    c.strides[0] = c.strides[1] * desc->num_kv_heads;
-  }
-  fill_dummy(c.k_pool); fill_dummy(c.v_pool); fill_dummy(c.block_table); fill_dummy(c.seq_lens);
-  CaptureScope scope;
-  const mfa_status_t st = paged_prefill(desc, (const void*)kPlanDummy, nullptr, nullptr, &c,
-                                        (float*)kPlanDummy, nullptr, nullptr);
-  if (st == MFA_SUCCESS) scope.copy_to(out);
-  return st;
+  return paged_plan(*desc, resolve_precisions(desc->base).mem[MFA_OPERAND_Q], cache, out,
+                    [&](const mfa_paged_kv_cache_t& c) {
+                      return paged_prefill(desc, (const void*)kPlanDummy, nullptr, nullptr, &c,
+                                           (float*)kPlanDummy, nullptr, nullptr);
+                    });
 }
+

@@ -756,6 +756,13 @@ class QuantizedAttention:
             _ptr(grad_value), _stream(stream)))
 
 
+def _paged_plan(fn, desc, cache) -> list[dict]:
+    """One of the three mfa_paged_*_plan queries: the launches as multihead_plan lists them."""
+    out = KernelPlan()
+    check(fn(ctypes.byref(desc), None if cache is None else ctypes.byref(cache), ctypes.byref(out)))
+    return out.as_list()
+
+
 def paged_decode_forward(desc: PagedDecodeDescriptor, query, cache: PagedKVCache, output,
                          logsumexp=None, query_strides=None, stream=None):
     """mfa_paged_decode_forward: split-KV decode over a paged, ragged K/V cache.  query
@@ -770,10 +777,7 @@ def paged_decode_forward(desc: PagedDecodeDescriptor, query, cache: PagedKVCache
 def paged_decode_plan(desc: PagedDecodeDescriptor, cache: Optional[PagedKVCache] = None) -> list[dict]:
     """mfa_paged_decode_plan: the kernels paged_decode_forward launches (see multihead_plan);
     without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
-    out = KernelPlan()
-    check(lib.mfa_paged_decode_plan(ctypes.byref(desc), None if cache is None else ctypes.byref(cache),
-                                    ctypes.byref(out)))
-    return out.as_list()
+    return _paged_plan(lib.mfa_paged_decode_plan, desc, cache)
 
 
 def paged_prefill_forward(desc: PagedPrefillDescriptor, query, cache: PagedKVCache, output,
@@ -794,11 +798,7 @@ def paged_prefill_plan(desc: PagedPrefillDescriptor,
                        cache: Optional[PagedKVCache] = None) -> list[dict]:
     """mfa_paged_prefill_plan: the kernel paged_prefill_forward launches (see multihead_plan);
     without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
-    out = KernelPlan()
-    check(lib.mfa_paged_prefill_plan(ctypes.byref(desc),
-                                     None if cache is None else ctypes.byref(cache),
-                                     ctypes.byref(out)))
-    return out.as_list()
+    return _paged_plan(lib.mfa_paged_prefill_plan, desc, cache)
 
 
 def paged_kv_append(desc: PagedAppendDescriptor, key, value, cache: PagedKVCache, new_lens=None,
@@ -820,11 +820,7 @@ def paged_kv_append_plan(desc: PagedAppendDescriptor,
                          cache: Optional[PagedKVCache] = None) -> list[dict]:
     """mfa_paged_kv_append_plan: the kernel paged_kv_append launches (see multihead_plan);
     without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
-    out = KernelPlan()
-    check(lib.mfa_paged_kv_append_plan(ctypes.byref(desc),
-                                       None if cache is None else ctypes.byref(cache),
-                                       ctypes.byref(out)))
-    return out.as_list()
+    return _paged_plan(lib.mfa_paged_kv_append_plan, desc, cache)
 
 
 def quantize(x, target: Precision, mode: QuantMode = QuantMode.tensorWise, rows=None, cols=None,

@@ -186,6 +186,23 @@ def assert_gradients_within_gate(got, ref, gate, rows=None, report=None):
         assert e[1] <= gate[name][1], f"{name} row error {e[1]:.3e} > gate {gate[name][1]:.3e}"
 
 
+def paged_cache(d, prec=None, page=64, **kw):
+    """A PagedKVCache shaped for the paged decode, prefill or append descriptor d, of d's 16-bit
+    type unless `prec` is given; its pointers are null (enough for a plan query)."""
+    if prec is None:
+        prec = d.input_precision if hasattr(d, "input_precision") else d.base.input_memory_precision
+    max_pages = -(-d.max_seq_len // page) if page else 1
+    return mfa.PagedKVCache.make(mfa.Precision(prec), page, max_pages,
+                                 max(1, max_pages * d.batch_size), d.num_kv_heads, d.head_dim, **kw)
+
+
+def paged_cache_full(d, **kw):
+    """paged_cache with every pointer set (aligned stand-ins, for calls the host rejects)."""
+    c = paged_cache(d, **kw)
+    c.k_pool, c.v_pool, c.block_table, c.seq_lens = 0x300000, 0x400000, 0x500000, 0x600000
+    return c
+
+
 def run_forward(Qn, Kn, Vn, prec=mfa.Precision.FP32, causal=False, window=None, scale=None,
                 amask=None, ranges=None, low_precision_intermediates=None, q_strides=None,
                 layout=None, dev="cuda:0"):

@@ -13,6 +13,7 @@ import subprocess
 import pytest
 
 import mfa_amd as mfa
+from harness import paged_cache as cache, paged_cache_full as full
 
 P = mfa.Precision
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,13 +25,6 @@ OK, INVALID_DESCRIPTOR, UNSUPPORTED, INVALID_ARGUMENT = 0, 1, 2, 4  # mfa_status
 def desc(B=2, H=8, Hkv=2, R=300, D=128, prec=P.FP16, max_seq_len=1000, **kw):
     base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, **kw)
     return mfa.PagedPrefillDescriptor.make(base, B, H, R, D, max_seq_len, Hkv=Hkv)
-
-
-def cache(d, prec=None, page=64, **kw):
-    prec = P(d.base.input_memory_precision) if prec is None else prec
-    max_pages = -(-d.max_seq_len // page) if page else 1
-    return mfa.PagedKVCache.make(prec, page, max_pages, max(1, max_pages * d.batch_size),
-                                 d.num_kv_heads, d.head_dim, **kw)
 
 
 def plan(d, c=None):
@@ -102,13 +96,6 @@ def status(d, c, query=0x100000, output=0x200000, strides=None, new_lens=None):
     if st != OK:
         assert mfa.lib.mfa_last_error(), "empty error message"
     return st
-
-
-def full(d, **kw):
-    """A cache with every pointer set (aligned stand-ins)."""
-    c = cache(d, **kw)
-    c.k_pool, c.v_pool, c.block_table, c.seq_lens = 0x300000, 0x400000, 0x500000, 0x600000
-    return c
 
 
 def test_null_pointers_are_invalid_arguments():
