@@ -642,6 +642,111 @@ mfa_status_t mfa_paged_prefill_forward(const mfa_paged_prefill_descriptor_t* des
 mfa_status_t mfa_paged_prefill_plan(const mfa_paged_prefill_descriptor_t* desc,
                                     const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
 
+/* ---------------------------------------------------------------------------------- */
+/* Paged MLA decode: absorbed attention over a paged latent cache.  (No reference      */
+/* counterpart.)                                                                       */
+
+/* The MLA latent held in fixed-size pages: one row of kv_latent_dim elements per key, shared by
+ * every head (the cache absorbed MLA keeps instead of K and V).  Pages, block_table and seq_lens
+ * mean what they mean in mfa_paged_kv_cache_t, and the kernels treat out-of-range device values
+ * the same way: seq_lens[b] is clamped to [0, min(max_seq_len, max_pages_per_seq * page_size)],
+ * page ids to [0, num_pages - 1].  A contiguous cache is one page per sequence: a dense
+ * [B, C_alloc, latent] tensor with C_alloc a power of two is strides = {C_alloc * latent, latent},
+ * page_size = C_alloc, max_pages_per_seq = 1, num_pages = B, block_table[b] = b. */
+typedef struct mfa_paged_latent_cache {
+  const void* pool;              /* device; page p, slot t, element d at
+                                    p*strides[0] + t*strides[1] + d (elements) */
+  int64_t strides[2];            /* page, token slot — element strides; d contiguous */
+  int32_t precision;             /* MFA_PRECISION_FP16 / BF16: the query's and the weights' type */
+  const int32_t* block_table;    /* device [batch][max_pages_per_seq]: pool page of logical page j */
+  const int32_t* seq_lens;       /* device [batch]: keys of each sequence */
+  uint32_t page_size;            /* keys per page: a power of two, >= 32 */
+  uint32_t max_pages_per_seq;
+  uint32_t num_pages;            /* pages in the pool */
+} mfa_paged_latent_cache_t;
+
+typedef struct mfa_paged_mla_descriptor {
+  mfa_attention_descriptor_t base;   /* scale, sparsity (NONE or CAUSAL), L precision */
+  uint32_t batch_size, num_heads;
+  uint32_t rows;                     /* R: query rows per head */
+  uint32_t head_dim, kv_latent_dim;  /* latent 256 or 512 */
+  uint32_t max_seq_len;              /* host-side bound on seq_lens[]; sizes the split and the scratch */
+  int32_t precision;                 /* MFA_PRECISION_FP16 / BF16: query, weights and pool */
+} mfa_paged_mla_descriptor_t;
+
+/* mfa_mla_forward_absorbed over a paged latent cache: the decode step of an MLA model served
+ * from pages, with no gather and no padding to the longest sequence.  query: dense [B, H, R, D]
+ * in `precision`; w_k / w_v: [latent, H * D]; output: dense FP32 [B, H, R, D]; logsumexp:
+ * nullable [B, H, R], FP16 when low_precision_intermediates, else FP32.  The softmax scale is the
+ * base descriptor's, or 1 / sqrt(head_dim).  Same result as attention over the decompressed
+ * K = latent * W_k, V = latent * W_v, up to the 16-bit rounding of Q * W_k^T.
+ * Lengths: len_b = clamp(cache->seq_lens[b], 0, min(max_seq_len, max_pages_per_seq * page_size)).
+ * Masks: MFA_SPARSITY_NONE — every row attends to keys 0 .. len_b - 1; MFA_SPARSITY_CAUSAL —
+ * row q attends to keys j <= len_b - R + q: mfa_paged_decode_forward's KV-cache convention (the
+ * R new tokens are already appended), not the top-left diagonal of mfa_mla_forward_absorbed.
+ * Sliding windows and sparse masks: MFA_ERR_UNSUPPORTED.
+ * Rows with no visible key — every row when len_b == 0, causal rows with len_b - R + q < 0 — get
+ * output rows of exact zeros and L = -FLT_MAX in FP32, -inf in FP16 (the paged calls' empty-row
+ * result), never NaN; every row of output and logsumexp is written, for any device values.
+ * Safety: the table lookup is clamped to the sequence's row and page ids to [0, num_pages - 1] —
+ * a wrong entry or length reads wrong data, never memory outside the pool; no row at or past
+ * len_b is fetched, and table entries of pages no key lies in are never used.
+ * Supported: latent 256 or 512; D % 8 == 0, D <= 256; a pool of `precision`, 16-byte aligned,
+ * like query and weights; strides >= 0 and multiples of 16 bytes, token stride >= latent and
+ * below 2^24 bytes; page size a power of two >= 32;
+ * min(max_seq_len, max_pages_per_seq * page_size) <= 2^30; max_pages_per_seq * B < 2^31; a
+ * positive softmax scale, untransposed operands; B * H * R < 2^31, B * H < 65536 (R == 1 and
+ * B > 1: B < 2^21).  batch_size == 0 or rows == 0 succeeds and launches nothing; the buffers may
+ * then be null.
+ * Three launches for any shape: the query projection mfa_mla_forward_absorbed uses for the shape,
+ * the latent-space attention split over the keys as that call splits S_kv =
+ * min(max_seq_len, max_pages_per_seq * page_size), and the merge that applies W_v.  Q * W_k^T
+ * and the split partials live in library scratch (mfa_release_scratch), sized by the descriptor
+ * and the cap alone.  Asynchronous on `stream`: no host read of device memory, no
+ * synchronisation; valid under stream capture after one warm-up call, so seq_lens += n,
+ * mfa_paged_latent_append and this call replay as one graph with new lengths. */
+mfa_status_t mfa_paged_mla_decode_forward(const mfa_paged_mla_descriptor_t* desc,
+                                          const void* query, const void* w_k, const void* w_v,
+                                          const mfa_paged_latent_cache_t* cache,
+                                          float* output, void* logsumexp, void* stream);
+/* The kernels that call launches (see mfa_multihead_plan).  cache == NULL plans a cache of
+ * 256-key pages in `precision`; NULL pointers inside a cache plan aligned buffers. */
+mfa_status_t mfa_paged_mla_decode_plan(const mfa_paged_mla_descriptor_t* desc,
+                                       const mfa_paged_latent_cache_t* cache,
+                                       mfa_kernel_plan_t* out);
+
+typedef struct mfa_paged_latent_append_descriptor {
+  int32_t precision;          /* MFA_PRECISION_FP16 / BF16: type of the new latent rows and the pool */
+  uint32_t batch_size;
+  uint32_t rows;              /* R: new-token rows per sequence (upper bound when new_lens is given) */
+  uint32_t kv_latent_dim;     /* 256 or 512 */
+  uint32_t max_seq_len;       /* same meaning as in mfa_paged_mla_descriptor_t */
+} mfa_paged_latent_append_descriptor_t;
+
+/* Appends new latent rows to a paged latent cache on the device: mfa_paged_kv_append with one
+ * pool and one "head" of kv_latent_dim elements.  latent: [B, R, latent] in `precision`
+ * (latent_strides: optional {batch, row} element strides, NULL = contiguous; d contiguous, both
+ * non-negative multiples of 8 elements, 16-byte aligned base — so the latent may be a slice of a
+ * wider projection output).  cache->seq_lens[b] is the length AFTER the append; with
+ * n_b = new_lens ? clamp(new_lens[b], 0, R) : R (new_lens: device [B], nullable), row r < n_b of
+ * sequence b is key position t = seq_lens[b] - n_b + r: slot t mod page_size of pool page
+ * clamp(block_table[b * max_pages_per_seq + t / page_size], 0, num_pages - 1).  Never written:
+ * rows r >= n_b; rows whose t lies outside [0, min(max_seq_len, max_pages_per_seq * page_size));
+ * any byte other than the latent elements of a written row; seq_lens, block_table and new_lens.
+ * The bits are unchanged.  The function writes through cache->pool: the struct's const is the
+ * reader's view.  The cache struct is checked by mfa_paged_mla_decode_forward's rules, and
+ * B * R < 2^31.  batch_size == 0 or rows == 0 succeeds and launches nothing.  Asynchronous on
+ * `stream`: no host read, no scratch, no synchronisation; valid under stream capture. */
+mfa_status_t mfa_paged_latent_append(const mfa_paged_latent_append_descriptor_t* desc,
+                                     const void* latent, const int64_t* latent_strides,
+                                     const int32_t* new_lens,
+                                     const mfa_paged_latent_cache_t* cache, void* stream);
+/* The kernel that call launches (see mfa_multihead_plan).  cache == NULL plans a cache of 256-key
+ * pages in `precision`; NULL pointers inside a cache plan aligned buffers. */
+mfa_status_t mfa_paged_latent_append_plan(const mfa_paged_latent_append_descriptor_t* desc,
+                                          const mfa_paged_latent_cache_t* cache,
+                                          mfa_kernel_plan_t* out);
+
 /* GPU runtime quantization (GEMMQuantization.swift:305-623 semantics, bit-exact; the
  * reference does this on the CPU in QuantizedTensor.from, :720-860).
  * input: device tensor of `count` elements in `input_precision` (FP32/FP16/BF16), viewed as

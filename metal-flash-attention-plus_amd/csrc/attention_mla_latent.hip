@@ -237,6 +237,235 @@ __global__ void __launch_bounds__(256, 2) mfa_mla_latent_kernel(LatentParams p) 
   }
 }
 
+// The same tile body over a paged latent cache (mfa_paged_mla_decode_forward; PagedKv's
+// conventions, one [page][LAT] row set per page).  What differs from the kernel above:
+//   * len_b = clamp(seq_lens[b], 0, p.Skv) is a device value, loaded once per workgroup on the
+//     scalar path; p.Skv is the host-side cap that sized the split;
+//   * key tiles start at multiples of 32 counted from key 0 (chunk is a multiple of 32 whenever
+//     there is more than one split), so a tile lies in one page: one block-table entry (lookup
+//     clamped to the sequence's row, id clamped to the pool) and one 64-bit base per tile, the
+//     next tile's entry fetched a tile ahead of its loads; rows at or past len_b are zeros and are
+//     not fetched;
+//   * causal is the KV-cache convention: row q of the Sq rows of a head attends to keys
+//     j <= klim = len_b − Sq + q (unmasked: klim = len_b − 1);
+//   * a row with no visible key in this split (klim < kbeg: every row of an empty sequence, the
+//     leading causal rows of a sequence shorter than Sq, rows whose keys end before the split)
+//     leaves the empty state (m = −FLT_MAX, l = 0, Õ = 0) — with the finite causal mask value it
+//     would otherwise carry a uniform average — so a row dead in every split merges to exact
+//     zeros and L at its floor;
+//   * always the split route: every workgroup writes its partial state, also with one split and
+//     also when it has no key (the scratch is not initialised); the merge applies W_v.
+typedef const __attribute__((address_space(4))) int32_t* latent_i32_ptr;
+
+template <class E, int LAT>
+__global__ void __launch_bounds__(256, 2) mfa_mla_latent_paged_kernel(LatentPagedParams pp) {
+  constexpr int BK = 32, NT = 256;
+  constexpr int WS = LAT / 4;              // latent dims per wave
+  constexpr int DS = WS / 16;              // MFMA k-steps of the wave's QK^T slice
+  constexpr int ND = WS / 32;              // O^T tiles per wave
+  constexpr int CPR = LAT / 8;             // 16-byte chunks per latent row
+  constexpr int CPT = BK * CPR / NT;       // chunks staged per thread
+  constexpr int TILEB = BK * LAT * 2;
+  constexpr int XST = 16;                  // floats per lane in the exchange area
+  using A = Arith16<E, LAT>;
+  using TT = Tile16<LAT>;
+  const LatentParams& p = pp.l;
+  const PagedKv& pg = pp.pg;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const tb0 = smem;                              // 2 latent tiles
+  float* const xb = reinterpret_cast<float*>(smem + 2 * TILEB);  // [4 waves][64 lanes][XST]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int split = blockIdx.x % p.nsplit;
+  const int bq = blockIdx.x / p.nsplit;
+  const int b = bq / p.nblk;
+  const int r0 = (bq % p.nblk) * 32;
+  const int r = r0 + l32;
+  const bool rvalid = r < p.R;
+  const int spos = rvalid ? r % p.Sq : 0;   // the row's index among its head's Sq rows
+
+  // The sequence's keys (uniform) and the last key this row sees.
+  const int len = min(max(((latent_i32_ptr)pg.seq_lens)[b], 0), p.Skv);
+  const int klim = p.causal ? len - p.Sq + spos : len - 1;
+
+  // Keys this block needs: all of the sequence, or up to its rows' largest limit.
+  int kend = len;
+  if (p.causal) {
+    const int rl = min(r0 + 31, p.R - 1);
+    const int smax = (r0 / p.Sq == rl / p.Sq) ? rl % p.Sq : p.Sq - 1;
+    kend = min(kend, len - p.Sq + smax + 1);
+  }
+  const int kbeg = split * p.chunk;
+  kend = min(kend, kbeg + p.chunk);
+
+  // Q̃ fragments of the wave's slice: d = w·WS + 16·ds + 8·hh + j.
+  i16x8 qf[DS];
+  {
+    const uint16_t* qrow = (const uint16_t*)p.q + ((int64_t)b * p.R + (rvalid ? r : 0)) * LAT;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) {
+      i16x8 v = i16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (rvalid) v = *reinterpret_cast<const i16x8*>(qrow + wave * WS + 16 * ds + 8 * hh);
+      qf[ds] = v;
+    }
+  }
+
+  // Block-table entry of the tile at key t (uniform), as stored; the lookup stays in the
+  // sequence's table row (the look-ahead runs past the last tile).
+  const latent_i32_ptr trow = (latent_i32_ptr)pg.block_table + (int64_t)b * pg.max_pages;
+  auto entry = [&](int t) { return trow[min(t >> pg.lg_page, pg.max_pages - 1)]; };
+  const int pmask = (1 << pg.lg_page) - 1;
+  // A tile is one buffer over its page rows below len_b (up to the last such row's end): a
+  // 16-byte load of a row at or past len_b lies outside it and returns zeros without a fetch.
+  // The token stride is below 2^24 bytes, so a tile's row offsets fit the 32-bit buffer offset.
+  const int tokb = (int)pp.tok_bytes;
+  const int voff0 = (tid / CPR) * tokb + 16 * (tid % CPR);   // chunk i: row tid / CPR + i·NT / CPR
+  const int vstep = (NT / CPR) * tokb;
+  uint4 stg[CPT];
+  auto load = [&](int t, int ent) {
+    const int page = min(max(ent, 0), pg.num_pages - 1);
+    const char* const base = (const char*)p.lat + (int64_t)page * pg.page_bytes +
+                             (int64_t)(t & pmask) * pp.tok_bytes;
+    const int nb = (min(len - t, BK) - 1) * tokb + LAT * 2;
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, nb, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < CPT; ++i)
+      stg[i] = __builtin_bit_cast(
+          uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff0 + i * vstep, 0, 0));
+  };
+  auto store = [&](char* tile) {
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int id = tid + NT * i;
+      *reinterpret_cast<uint4*>(tile + TT::off(id / CPR, id % CPR)) = stg[i];
+    }
+  };
+
+  f32x16 o[ND];
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt) o[dt] = zero16();
+  float m = -kFltMax, lh = 0.f;
+  const float c = p.c_log2;
+
+  int ent_next = 0;
+  if (kbeg < kend) {
+    load(kbeg, entry(kbeg));
+    store(tb0);
+    ent_next = entry(kbeg + BK);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int t = kbeg; t < kend; t += BK) {
+    const bool has_next = t + BK < kend;
+    if (has_next) load(t + BK, ent_next);
+    ent_next = entry(t + 2 * BK);
+    const char* kt = tb0 + cur * TILEB;
+
+    // Partial S^T over this wave's latent slice.
+    f32x16 sp = zero16();
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds)
+      sp = A::mma(A::read_row(kt, l32, wave * DS + ds, hh), qf[ds], sp);
+    // Exchange: each lane's 16 partial values contiguous ([wave][lane][16 floats]); the four
+    // 16-byte chunks are rotated by (lane >> 2) & 3 so the lanes of a ds_read_b128 group hit
+    // distinct banks.
+    const int xsw = (lane >> 2) & 3;
+    {
+      float* dst = xb + (wave * 64 + lane) * XST;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<f32x4*>(dst + 4 * (q ^ xsw)) =
+            f32x4{sp[4 * q], sp[4 * q + 1], sp[4 * q + 2], sp[4 * q + 3]};
+    }
+    __syncthreads();
+    f32x16 s;
+    {
+      f32x4 part[4][4];
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          part[w][q] = *reinterpret_cast<const f32x4*>(xb + (w * 64 + lane) * XST + 4 * (q ^ xsw));
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          s[4 * q + e] = ((part[0][q][e] + part[1][q][e]) + part[2][q][e]) + part[3][q][e];
+    }
+
+    if (t + BK > len || (p.causal && t + BK - 1 > klim)) {
+      MFA_KEEP_BRANCH();
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int key = t + acc_row(i, hh);
+        if (p.causal && key > klim) s[i] = kMaskValue;
+        if (key >= len) s[i] = -__builtin_inff();
+      }
+    }
+    float mx = s[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
+    const float m_tile = cross_half_max(mx) * c;
+    if (m_tile > m) {
+      const float corr = __builtin_amdgcn_exp2f(m - m_tile);
+      m = m_tile;
+      lh *= corr;
+#pragma unroll
+      for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[dt][i] *= corr;
+    }
+    float rs = 0.f;
+    if (m < kMaskLevel) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        s[i] = __builtin_amdgcn_exp2f(mul_rn(s[i], c) - m);
+        rs += s[i];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        s[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, -m));
+        rs += s[i];
+      }
+    }
+    lh += rs;
+    // O^T += latent[:, slice]^T · P^T
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const i16x8 pb = A::pack(s, ks);
+#pragma unroll
+      for (int dt = 0; dt < ND; ++dt)
+        o[dt] = A::mma(A::read_tr(kt, 0, ks, wave * WS + 32 * dt, lane), pb, o[dt]);
+    }
+    if (has_next) store(tb0 + (cur ^ 1) * TILEB);
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // Partial state of this key split: Õ unnormalised, (m, l) for the merge pass; the empty state
+  // for a row that saw no key here.
+  float lp = cross_half_sum(lh);
+  if (klim < kbeg) {
+    m = -kFltMax;
+    lp = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt) o[dt] = zero16();
+  }
+  if (!rvalid) return;
+  const int64_t prow = ((int64_t)b * p.nsplit + split) * p.R + r;
+  float* op = p.opart + prow * LAT + wave * WS;
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      *reinterpret_cast<float4*>(op + dt * 32 + 8 * g + 4 * hh) =
+          make_float4(o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]);
+  if (wave == 0 && hh == 0) p.mlpart[prow] = make_float2(m, lp);
+}
+
 // Merge of the key splits (flash-decoding): M = max m_s, w_s = exp2(m_s − M),
 // Õ = Σ w_s Õ_s / Σ w_s l_s, L = M + log2 Σ w_s l_s.  MNB rows (the same query row r of MNB
 // consecutive batch items) per 256-thread workgroup, launched with MNB = 1.  The split states
@@ -388,6 +617,18 @@ static hipError_t launch_latent(const LatentParams& p, hipStream_t stream) {
   return launch(mfa_mla_latent_merge_kernel<E, LAT, 1>, dim3(p.B * p.R), dim3(MNT), 0, stream, p);
 }
 
+// The paged route: partials from every split, then the merge with W_v — also for one split.
+template <class E, int LAT>
+static hipError_t launch_latent_paged(const LatentPagedParams& p, hipStream_t stream) {
+  constexpr int LDS = 2 * 32 * LAT * 2 + 4 * 64 * 16 * 4;
+  const LatentParams& l = p.l;
+  if (!l.opart || !l.mlpart || !l.wv || l.nsplit < 1) return hipErrorInvalidValue;
+  hipError_t e = launch(mfa_mla_latent_paged_kernel<E, LAT>, dim3(l.nblk * l.B * l.nsplit),
+                        dim3(256), LDS, stream, p);
+  if (e != hipSuccess) return e;
+  return launch(mfa_mla_latent_merge_kernel<E, LAT, 1>, dim3(l.B * l.R), dim3(MNT), 0, stream, l);
+}
+
 // Decode query projection Q̃[b, h, :] = q[b, h, :] · W_k[:, h·D : (h+1)·D]ᵀ (S_q = 1): a workgroup
 // takes one head, QC latent columns and 32 batch rows; the W_k slice [QC][D] and the query rows
 // [32][D] sit in LDS (rows padded by 16 B), each thread accumulates QC/8 columns of one row in
@@ -459,15 +700,14 @@ hipError_t mla_qproj_dispatch(const void* q, const void* wk, void* qt, int B, in
     return hipErrorNotSupported;
   const dim3 grid(H, (Lat + QC - 1) / QC, (B + 31) / 32);
   const size_t lds = (size_t)(QC + 32) * (D * 2 + 16);
+  // Through launch(): the paged MLA plan lists this launch, and the launch log records it.
   if (elem == P_FP16)
-    hipLaunchKernelGGL(mfa_mla_qproj_kernel<F16>, grid, dim3(256), lds, stream,
-                       (const uint16_t*)q, (const uint16_t*)wk, (uint16_t*)qt, B, H, D, Lat);
-  else if (elem == P_BF16)
-    hipLaunchKernelGGL(mfa_mla_qproj_kernel<BF16>, grid, dim3(256), lds, stream,
-                       (const uint16_t*)q, (const uint16_t*)wk, (uint16_t*)qt, B, H, D, Lat);
-  else
-    return hipErrorNotSupported;
-  return hipGetLastError();
+    return launch(mfa_mla_qproj_kernel<F16>, grid, dim3(256), lds, stream, (const uint16_t*)q,
+                  (const uint16_t*)wk, (uint16_t*)qt, B, H, D, Lat);
+  if (elem == P_BF16)
+    return launch(mfa_mla_qproj_kernel<BF16>, grid, dim3(256), lds, stream, (const uint16_t*)q,
+                  (const uint16_t*)wk, (uint16_t*)qt, B, H, D, Lat);
+  return hipErrorNotSupported;
 }
 
 hipError_t mla_latent_dispatch(const LatentParams& p, int elem, int lat, hipStream_t stream) {
@@ -478,6 +718,19 @@ hipError_t mla_latent_dispatch(const LatentParams& p, int elem, int lat, hipStre
   return hipErrorNotSupported;
 }
 
+hipError_t mla_latent_paged_dispatch(const LatentPagedParams& p, int elem, int lat,
+                                     hipStream_t stream) {
+  if (lat == 512 && elem == P_FP16) return launch_latent_paged<F16, 512>(p, stream);
+  if (lat == 512 && elem == P_BF16) return launch_latent_paged<BF16, 512>(p, stream);
+  if (lat == 256 && elem == P_FP16) return launch_latent_paged<F16, 256>(p, stream);
+  if (lat == 256 && elem == P_BF16) return launch_latent_paged<BF16, 256>(p, stream);
+  return hipErrorNotSupported;
+}
+
+template __global__ void mfa_mla_latent_paged_kernel<F16, 512>(LatentPagedParams);
+template __global__ void mfa_mla_latent_paged_kernel<BF16, 512>(LatentPagedParams);
+template __global__ void mfa_mla_latent_paged_kernel<F16, 256>(LatentPagedParams);
+template __global__ void mfa_mla_latent_paged_kernel<BF16, 256>(LatentPagedParams);
 template __global__ void mfa_mla_latent_kernel<F16, 512>(LatentParams);
 template __global__ void mfa_mla_latent_merge_kernel<F16, 512, 1>(LatentParams);
 template __global__ void mfa_mla_latent_merge_kernel<BF16, 512, 1>(LatentParams);

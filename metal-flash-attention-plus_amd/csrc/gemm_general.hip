@@ -30,6 +30,7 @@
 #include "mfa_device.h"
 #include "mfa_params.h"
 #include "mfa_dispatch.h"
+#include "mfa_launch.h"
 #include <type_traits>
 
 namespace mfa {
@@ -320,9 +321,7 @@ hipError_t gemm_general_dispatch(const GemmGParams& p, int batch, hipStream_t st
   const int lay = (p.trans_a ? 1 : 0) | (p.trans_b ? 0 : 2);
 #define MFA_GG(CTV, L)                                                                      \
   case L: {                                                                                 \
-    auto k = mfa_gemm_general_kernel<CTV, L>;                                               \
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, p);                                   \
-    break;                                                                                  \
+    return launch(mfa_gemm_general_kernel<CTV, L>, grid, dim3(256), 0, stream, p);          \
   }
   switch (gemm_general_compute(p.prec_a, p.prec_b)) {
     case P_FP16:
@@ -333,10 +332,9 @@ hipError_t gemm_general_dispatch(const GemmGParams& p, int batch, hipStream_t st
       break;
 #undef MFA_GG
     default:
-      hipLaunchKernelGGL(mfa_gemm_general_kernel<P_FP32>, grid, dim3(256), 0, stream, p);
       break;
   }
-  return hipGetLastError();
+  return launch(mfa_gemm_general_kernel<P_FP32>, grid, dim3(256), 0, stream, p);
 }
 
 #define MFA_GG_INST(CTV)                                                   \

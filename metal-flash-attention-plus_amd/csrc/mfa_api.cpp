@@ -1699,6 +1699,41 @@ AbsorbedLayout absorbed_layout(int B, int H, int Sq, int Skv, int Lat) {
   return a;
 }
 
+// One general-GEMM launch over all (b, h) of the absorbed path: W_k / W_v slices depend on h
+// only (ldb = H·D, batch stride D, bmod = H).
+mfa_status_t absorbed_gemm(const void* a, const void* w, void* c, int M, int N, int K, int lda,
+                           int ldc, int trans_b, int prec, int prec_c, int64_t sa, int64_t sc,
+                           int nbatch, int bmod, int H, int D, hipStream_t s) {
+  mfa::GemmGParams g;
+  memset(&g, 0, sizeof(g));
+  g.a = a; g.b = w; g.c = c;
+  g.M = M; g.N = N; g.K = K;
+  g.lda = lda; g.ldb = H * D; g.ldc = ldc;
+  g.sa = sa; g.sb = D; g.sc = sc;
+  g.prec_a = g.prec_b = prec; g.prec_c = prec_c;
+  g.esz_a = g.esz_b = 2; g.esz_c = prec_c == MFA_PRECISION_FP32 ? 4 : 2;
+  g.trans_b = trans_b;
+  g.bmod = bmod;
+  return hip_status(mfa::gemm_general_dispatch(g, nbatch, s), "absorbed MLA GEMM launch");
+}
+
+// Q̃[b, h] (Sq x Lat) = Q[b, h] (Sq x D) · W_k[:, hD:(h+1)D]ᵀ for every (b, h), one launch.
+// Decode (S_q = 1, B > 1): per head, the B query rows are one strided [B, D] matrix, so each
+// head's weight slice is read once (M = B) instead of once per batch item — the projection
+// kernel, or the general GEMM where it does not take the shape.  Otherwise the general GEMM
+// batched over (b, h).
+mfa_status_t absorbed_project_query(const void* query, const void* w_k, void* qt, int B, int H,
+                                    int Sq, int D, int Lat, int prec, hipStream_t s) {
+  if (Sq == 1 && B > 1) {
+    const hipError_t e = mfa::mla_qproj_dispatch(query, w_k, qt, B, H, D, Lat, elem_of(prec), s);
+    if (e != hipErrorNotSupported) return hip_status(e, "absorbed MLA query projection launch");
+    return absorbed_gemm(query, w_k, qt, B, Lat, D, H * D, H * Lat, 1, prec, prec, D, Lat, H, 0,
+                         H, D, s);
+  }
+  return absorbed_gemm(query, w_k, qt, Sq, Lat, D, D, Lat, 1, prec, prec, (int64_t)Sq * D,
+                       (int64_t)Sq * Lat, B * H, H, H, D, s);
+}
+
 }  // namespace
 
 extern "C" size_t mfa_mla_absorbed_workspace_size(const mfa_mla_descriptor_t* desc) {
@@ -1746,34 +1781,13 @@ extern "C" mfa_status_t mfa_mla_forward_absorbed(const mfa_mla_descriptor_t* des
   auto general = [&](const void* a, const void* w, void* c, int M, int N, int K, int lda,
                      int ldc, int trans_b, int prec_c, int64_t sa, int64_t sc, int nbatch,
                      int bmod) {
-    mfa::GemmGParams g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.b = w; g.c = c;
-    g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = H * D; g.ldc = ldc;
-    g.sa = sa; g.sb = D; g.sc = sc;
-    g.prec_a = g.prec_b = prec; g.prec_c = prec_c;
-    g.esz_a = g.esz_b = 2; g.esz_c = prec_c == MFA_PRECISION_FP32 ? 4 : 2;
-    g.trans_b = trans_b;
-    g.bmod = bmod;
-    return hip_status(mfa::gemm_general_dispatch(g, nbatch, s), "absorbed MLA GEMM launch");
+    return absorbed_gemm(a, w, c, M, N, K, lda, ldc, trans_b, prec, prec_c, sa, sc, nbatch, bmod,
+                         H, D, s);
   };
-  // Decode (S_q = 1): per head, the B query rows are one strided [B, D] matrix, so each head's
-  // weight slice is read once (M = B) instead of once per batch item.
   const bool decode = Sq == 1 && B > 1;
-  if (decode) {
-    const hipError_t e = mfa::mla_qproj_dispatch(query, w_k, qt, B, H, D, Lat, elem_of(prec), s);
-    if (e != hipErrorNotSupported) {
-      if ((st = hip_status(e, "absorbed MLA query projection launch")) != MFA_SUCCESS) return st;
-    } else if ((st = general(query, w_k, qt, B, Lat, D, H * D, H * Lat, 1, prec, D, Lat, H,
-                             0)) != MFA_SUCCESS) {
-      return st;
-    }
-  } else if (B > 1) {
-    if ((st = general(query, w_k, qt, Sq, Lat, D, D, Lat, 1, prec, (int64_t)Sq * D,
-                      (int64_t)Sq * Lat, B * H, H)) != MFA_SUCCESS)
-      return st;
-  }
+  if (B > 1 &&
+      (st = absorbed_project_query(query, w_k, qt, B, H, Sq, D, Lat, prec, s)) != MFA_SUCCESS)
+    return st;
   // Q̃[b,h] (Sq x Lat) = Q[b,h] (Sq x D) · W_k[:, hD:(h+1)D]ᵀ, batched over h.
   for (int b = 0; b < B && B == 1; ++b) {
     mfa_gemm_descriptor_t g;
@@ -1862,10 +1876,12 @@ struct PagedCacheView {
 };
 
 // Everything that needs no buffer.  prec16 is the caller's 16-bit operand precision and `whose`
-// the word its message uses for it ("query's", "input's").
+// the word its message uses for it ("query's", "input's").  row > 0: a token slot holds `row`
+// elements that are not one head's D (the latent cache, paged_latent_view) — the head-dimension
+// rule is the caller's and the token stride is held against `row`.
 mfa_status_t paged_cache_view(const char* what, const mfa_paged_kv_cache_t& c, int64_t B, int64_t D,
                               uint32_t max_seq_len, int prec16, const char* whose, bool allow_i8,
-                              PagedCacheView* v) {
+                              PagedCacheView* v, int64_t row = 0) {
   const uint32_t ps = c.page_size;
   if (ps < 32 || (ps & (ps - 1)) != 0)
     return fail(MFA_ERR_UNSUPPORTED, "%s: page size %u is not a power of two >= 32", what, ps);
@@ -1881,7 +1897,7 @@ mfa_status_t paged_cache_view(const char* what, const mfa_paged_kv_cache_t& c, i
   if (!i8 && cprec != prec16)
     return fail(MFA_ERR_UNSUPPORTED, "%s: %scache precision %d differs from the %s %d", what,
                 allow_i8 ? "16-bit " : "", cprec, whose, prec16);
-  if (D % (i8 ? 16 : 8) != 0 || D > 256)
+  if (row == 0 && (D % (i8 ? 16 : 8) != 0 || D > 256))
     return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of %d, at most 256)",
                 what, (long long)D, i8 ? 16 : 8);
   if (i8 && (c.k_zero_point < -128 || c.k_zero_point > 128 || c.v_zero_point < -128 ||
@@ -1891,7 +1907,7 @@ mfa_status_t paged_cache_view(const char* what, const mfa_paged_kv_cache_t& c, i
   for (int i = 0; i < 3; ++i)
     if (c.strides[i] < 0 || (c.strides[i] * es) % 16 != 0)
       return fail(MFA_ERR_UNSUPPORTED, "%s: cache stride %d is not a multiple of 16 bytes", what, i);
-  if (c.strides[2] < D || c.strides[2] * es >= ((int64_t)1 << 24))
+  if (c.strides[2] < (row ? row : D) || c.strides[2] * es >= ((int64_t)1 << 24))
     return fail(MFA_ERR_UNSUPPORTED, "%s: token stride %lld", what, (long long)c.strides[2]);
   const int64_t cap = std::min<int64_t>(max_seq_len, (int64_t)c.max_pages_per_seq * ps);
   if (cap > ((int64_t)1 << 30))
@@ -2105,7 +2121,7 @@ mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void*
   p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
   p.cap = (int)cv.cap;
   p.rows_total = (int)(B * R);
-  return hip_status(mfa::paged_append_dispatch(p, iprec, cv.i8, stream),
+  return hip_status(mfa::paged_append_dispatch(p, iprec, cv.i8, 2, stream),
                     "mfa_paged_kv_append launch");
 }
 
@@ -2174,6 +2190,204 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
   return hip_status(e, "mfa_fwd (paged prefill) launch");
 }
 
+// -----------------------------------------------------------------------------------------
+// The paged latent cache of absorbed MLA (no reference counterpart): one [page][slot][latent]
+// pool shared by every head, read by mfa_mla_latent_paged_kernel and written by the append
+// kernel with one operand.
+
+// A checked mfa_paged_latent_cache_t: the K/V view's rules on a stand-in cache with one pool, no
+// head stride and token slots of Lat elements (stride index 2 in a message is the token stride).
+mfa_status_t paged_latent_view(const char* what, const mfa_paged_latent_cache_t& c, int64_t B,
+                               int64_t Lat, uint32_t max_seq_len, int prec16, const char* whose,
+                               PagedCacheView* v) {
+  mfa_paged_kv_cache_t kv;
+  memset(&kv, 0, sizeof(kv));
+  kv.k_pool = kv.v_pool = c.pool;
+  kv.strides[0] = c.strides[0];
+  kv.strides[2] = c.strides[1];
+  kv.precision = c.precision;
+  kv.k_scale = kv.v_scale = 1.f;
+  kv.block_table = c.block_table;
+  kv.seq_lens = c.seq_lens;
+  kv.page_size = c.page_size;
+  kv.max_pages_per_seq = c.max_pages_per_seq;
+  kv.num_pages = c.num_pages;
+  return paged_cache_view(what, kv, B, Lat, max_seq_len, prec16, whose, false, v, Lat);
+}
+
+// paged_cache_buffers for the one-pool cache.
+mfa_status_t paged_latent_buffers(const char* what, const mfa_paged_latent_cache_t& c,
+                                  const char* own, bool have_own) {
+  if (!have_own || !c.pool || !c.block_table || !c.seq_lens)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "%s requires %s, the pool, block_table and seq_lens",
+                what, own);
+  if (!aligned16(c.pool))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: the pool must be 16-byte aligned", what);
+  return MFA_SUCCESS;
+}
+
+// paged_plan for the one-pool cache: without one, a dense 16-bit cache of 256-key pages.
+template <class Desc, class Run>
+mfa_status_t paged_latent_plan(const Desc& d, const mfa_paged_latent_cache_t* cache,
+                               mfa_kernel_plan_t* out, Run run) {
+  memset(out, 0, sizeof(*out));
+  mfa_paged_latent_cache_t c;
+  if (cache) {
+    c = *cache;
+  } else {
+    memset(&c, 0, sizeof(c));
+    c.precision = d.precision;
+    c.page_size = 256;
+    c.max_pages_per_seq = (d.max_seq_len + 255) / 256;
+    c.num_pages = std::max<uint32_t>(1, c.max_pages_per_seq * d.batch_size);
+    c.strides[1] = d.kv_latent_dim;
+    c.strides[0] = (int64_t)c.page_size * d.kv_latent_dim;
+  }
+  fill_dummy(c.pool); fill_dummy(c.block_table); fill_dummy(c.seq_lens);
+  CaptureScope scope;
+  const mfa_status_t st = run(c);
+  if (st == MFA_SUCCESS) scope.copy_to(out);
+  return st;
+}
+
+// Absorbed MLA decode over the paged latent: Q̃ = Q·W_kᵀ (the dense call's launch for the
+// shape), mfa_mla_latent_paged_kernel over absorbed_layout's split at S_kv = cap, and the merge
+// that applies W_v — three launches for any split count.  Q̃ and the partials live in library
+// scratch slot 16, sized by the descriptor alone.
+mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void* query,
+                              const void* w_k, const void* w_v,
+                              const mfa_paged_latent_cache_t* cache, float* output,
+                              void* logsumexp, hipStream_t stream) {
+  const char* const what = "paged MLA decode";
+  if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
+  const mfa_attention_descriptor_t& base = desc->base;
+  const int64_t B = desc->batch_size, H = desc->num_heads, R = desc->rows;
+  const int64_t D = desc->head_dim, Lat = desc->kv_latent_dim;
+  if (H == 0 || D == 0 || Lat == 0 || desc->max_seq_len == 0 || cache->max_pages_per_seq == 0 ||
+      cache->num_pages == 0)
+    return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: empty shape", what);
+  const int prec = desc->precision;
+  if (prec != MFA_PRECISION_FP16 && prec != MFA_PRECISION_BF16)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: precision %d (FP16 or BF16)", what, prec);
+  if (Lat != 256 && Lat != 512)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: latent dimension %lld (256 or 512)", what,
+                (long long)Lat);
+  PagedCacheView cv;
+  mfa_status_t st =
+      paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "descriptor's", &cv);
+  if (st != MFA_SUCCESS) return st;
+  if (D % 8 != 0 || D > 256)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of 8, at most 256)",
+                what, (long long)D);
+  if (base.has_sparse_mask || (base.sparsity_pattern != MFA_SPARSITY_NONE &&
+                               base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);
+  if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
+  const float scale = resolve_scale(base, (int)D);
+  if (!(scale > 0.f) || !(1.442695041f * scale > 0.f))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
+  if (B * H * R >= ((int64_t)1 << 31))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
+  // The projection's grid z: 32 batch rows per workgroup (R = 1), or one (b, h) each.
+  if ((R == 1 && B > 1 ? (B + 31) / 32 : B * H) >= 65536)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: %lld x %lld (batch, head) pairs exceed the grid", what,
+                (long long)B, (long long)H);
+  if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
+  if ((st = paged_latent_buffers(what, *cache, "query, w_k, w_v, output",
+                                 query && w_k && w_v && output)) != MFA_SUCCESS)
+    return st;
+  if (!aligned16(query) || !aligned16(w_k) || !aligned16(w_v))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: query and weights must be 16-byte aligned", what);
+
+  const AbsorbedLayout al = absorbed_layout((int)B, (int)H, (int)R, (int)cv.cap, (int)Lat);
+  if ((int64_t)al.nblk * B * al.nsplit >= ((int64_t)1 << 31))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: the key splits exceed the grid", what);
+  const size_t prows = (size_t)B * al.nsplit * H * R;
+  const size_t qbytes = (al.qt_bytes + 255) & ~(size_t)255, obytes = prows * Lat * 4;
+  void* ws = (void*)kPlanDummy;
+  if (!mfa::plan_capture() &&
+      (st = scratch(qbytes + obytes + prows * 8, &ws, 16, stream)) != MFA_SUCCESS)
+    return st;
+  char* const qt = (char*)ws;
+  if ((st = absorbed_project_query(query, w_k, qt, (int)B, (int)H, (int)R, (int)D, (int)Lat, prec,
+                                   stream)) != MFA_SUCCESS)
+    return st;
+
+  mfa::LatentPagedParams p;
+  memset(&p, 0, sizeof(p));
+  p.l.q = qt;
+  p.l.lat = cache->pool;
+  p.l.l = logsumexp;
+  p.l.l_f16 = resolve_precisions(base).mem[MFA_OPERAND_L] == MFA_PRECISION_FP16;
+  p.l.B = (int)B; p.l.R = (int)(H * R); p.l.Sq = (int)R; p.l.Skv = (int)cv.cap;
+  p.l.nblk = al.nblk;
+  p.l.c_log2 = 1.442695041f * scale;
+  p.l.causal = base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
+  p.l.nsplit = al.nsplit;
+  p.l.chunk = al.chunk;
+  p.l.opart = (float*)(qt + qbytes);
+  p.l.mlpart = (float2*)(qt + qbytes + obytes);
+  p.l.wv = w_v;
+  p.l.out = output;
+  p.l.H = (int)H; p.l.D = (int)D;
+  p.pg = cv.pg;
+  p.tok_bytes = cache->strides[1] * cv.es;
+  const hipError_t e = mfa::mla_latent_paged_dispatch(p, elem_of(prec), (int)Lat, stream);
+  if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
+  return hip_status(e, "paged MLA latent attention launch");
+}
+
+// The write side: paged_append's kernel with one operand — one pool, one "head" of Lat
+// elements, no head stride.
+mfa_status_t paged_latent_append(const mfa_paged_latent_append_descriptor_t* desc,
+                                 const void* latent, const int64_t* latent_strides,
+                                 const int32_t* new_lens, const mfa_paged_latent_cache_t* cache,
+                                 hipStream_t stream) {
+  const char* const what = "paged latent append";
+  if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
+  const int64_t B = desc->batch_size, R = desc->rows, Lat = desc->kv_latent_dim;
+  if (Lat == 0 || desc->max_seq_len == 0 || cache->max_pages_per_seq == 0 || cache->num_pages == 0)
+    return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: empty shape", what);
+  const int prec = desc->precision;
+  if (prec != MFA_PRECISION_FP16 && prec != MFA_PRECISION_BF16)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: precision %d (FP16 or BF16)", what, prec);
+  if (Lat != 256 && Lat != 512)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: latent dimension %lld (256 or 512)", what,
+                (long long)Lat);
+  PagedCacheView cv;
+  mfa_status_t st =
+      paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "input's", &cv);
+  if (st != MFA_SUCCESS) return st;
+  if (B * R >= ((int64_t)1 << 31))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: too many rows", what);
+  if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to write; the buffers may be null
+  if ((st = paged_latent_buffers(what, *cache, "latent", latent != nullptr)) != MFA_SUCCESS)
+    return st;
+
+  const int64_t dense[2] = {R * Lat, Lat};
+  const int64_t* s = latent_strides ? latent_strides : dense;
+  if (!aligned16(latent))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: latent rows must be 16-byte aligned", what);
+  for (int j = 0; j < 2; ++j)
+    if (s[j] < 0 || s[j] % 8 != 0)
+      return fail(MFA_ERR_UNSUPPORTED, "%s: latent stride %d is not a multiple of 8 elements",
+                  what, j);
+  mfa::PagedAppendParams p;
+  memset(&p, 0, sizeof(p));
+  p.src[0] = latent;
+  p.s_sb[0] = s[0] * 2; p.s_ss[0] = s[1] * 2;
+  p.pool[0] = const_cast<void*>(cache->pool);
+  p.scale[0] = 1.f;
+  p.pg = cv.pg;
+  p.new_lens = new_lens;
+  p.tok_bytes = cache->strides[1] * cv.es;
+  p.Hkv = 1; p.R = (int)R; p.D = (int)Lat;
+  p.cap = (int)cv.cap;
+  p.rows_total = (int)(B * R);
+  return hip_status(mfa::paged_append_dispatch(p, prec, false, 1, stream),
+                    "mfa_paged_latent_append launch");
+}
+
 }  // namespace
 
 extern "C" mfa_status_t mfa_paged_decode_forward(const mfa_paged_decode_descriptor_t* desc,
@@ -2231,5 +2445,41 @@ extern "C" mfa_status_t mfa_paged_prefill_plan(const mfa_paged_prefill_descripto
                       return paged_prefill(desc, (const void*)kPlanDummy, nullptr, nullptr, &c,
                                            (float*)kPlanDummy, nullptr, nullptr);
                     });
+}
+
+extern "C" mfa_status_t mfa_paged_mla_decode_forward(const mfa_paged_mla_descriptor_t* desc,
+                                                     const void* query, const void* w_k,
+                                                     const void* w_v,
+                                                     const mfa_paged_latent_cache_t* cache,
+                                                     float* output, void* logsumexp,
+                                                     void* stream) {
+  return paged_mla_decode(desc, query, w_k, w_v, cache, output, logsumexp, (hipStream_t)stream);
+}
+
+extern "C" mfa_status_t mfa_paged_mla_decode_plan(const mfa_paged_mla_descriptor_t* desc,
+                                                  const mfa_paged_latent_cache_t* cache,
+                                                  mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  const void* const vd = (const void*)kPlanDummy;
+  return paged_latent_plan(*desc, cache, out, [&](const mfa_paged_latent_cache_t& c) {
+    return paged_mla_decode(desc, vd, vd, vd, &c, (float*)kPlanDummy, nullptr, nullptr);
+  });
+}
+
+extern "C" mfa_status_t mfa_paged_latent_append(const mfa_paged_latent_append_descriptor_t* desc,
+                                                const void* latent, const int64_t* latent_strides,
+                                                const int32_t* new_lens,
+                                                const mfa_paged_latent_cache_t* cache,
+                                                void* stream) {
+  return paged_latent_append(desc, latent, latent_strides, new_lens, cache, (hipStream_t)stream);
+}
+
+extern "C" mfa_status_t mfa_paged_latent_append_plan(
+    const mfa_paged_latent_append_descriptor_t* desc, const mfa_paged_latent_cache_t* cache,
+    mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return paged_latent_plan(*desc, cache, out, [&](const mfa_paged_latent_cache_t& c) {
+    return paged_latent_append(desc, (const void*)kPlanDummy, nullptr, nullptr, &c, nullptr);
+  });
 }
 

@@ -81,8 +81,9 @@ hipError_t fwd_prefill_paged_dispatch(const FwdParams& p, const PagedKv& pg,
                                       const int32_t* new_lens, int elem, hipStream_t stream);
 // The write side of that cache (paged_append.hip): one launch scatters the new key and value
 // rows (16-bit, type `elem`) into 16-bit pools of the same type or, with i8, quantises them into
-// per-tensor INT8 pools.
-hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8,
+// per-tensor INT8 pools.  operands = 2: key and value; 1: index 0 of each pair alone (the latent
+// pool of mfa_paged_latent_append, one "head" of kv_latent_dim elements).
+hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8, int operands,
                                  hipStream_t stream);
 // FP16 Q with per-tensor INT8 / INT4 K/V (src SRC_I8 / SRC_I4) widened on load inside the
 // shared-tile loop (attention_fwd_kv8.hip); D <= 128 padded to 128, no masks.
@@ -111,6 +112,10 @@ hipError_t fwd_i8mma_dispatch(const FwdParams& p, int elem, hipStream_t stream);
 hipError_t gemm_dispatch(const GemmParams& p, int prec_ab, int batch, hipStream_t stream);
 // MLA latent-space attention (attention_mla_latent.hip); lat = 256 or 512.
 hipError_t mla_latent_dispatch(const LatentParams& p, int elem, int lat, hipStream_t stream);
+// The same over a paged latent cache: the paged latent kernel, then the merge with W_v, for any
+// split count (p.l.nsplit >= 1).
+hipError_t mla_latent_paged_dispatch(const LatentPagedParams& p, int elem, int lat,
+                                     hipStream_t stream);
 // Decode (S_q = 1) query projection of the absorbed MLA path; hipErrorNotSupported when the
 // shapes or alignment do not fit (the caller falls back to the general GEMM).
 hipError_t mla_qproj_dispatch(const void* q, const void* wk, void* qt, int B, int H, int D,

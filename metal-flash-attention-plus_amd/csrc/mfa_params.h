@@ -176,6 +176,15 @@ struct LatentParams {
   int32_t H, D;
 };
 
+// The same attention over a paged latent cache (mfa_mla_latent_paged_kernel): l.lat is the page
+// pool, l.Skv the host-side cap on every length, l.Sq the query rows per head (row q attends to
+// keys j <= len_b - Sq + q when causal).  Always the split route: l.opart / l.mlpart are set.
+struct LatentPagedParams {
+  LatentParams l;
+  PagedKv pg;          // one [page][LAT] row set per page: head_bytes is unused
+  int64_t tok_bytes;   // byte stride between the token slots of a page
+};
+
 // General GEMM (gemm_general.hip): any FP32/FP16/BF16 mix, transposes, leading dimensions.
 struct GemmGParams {
   const void* a;

@@ -8,6 +8,9 @@
 // Rows r >= n_b and rows whose t is outside [0, cap) are dropped; a written row never leaves the
 // pools (the page id is clamped to them as the readers clamp it).
 //
+// mfa_paged_latent_append is the same kernel with one operand (grid.y = 1): the MLA latent pool
+// as a key pool with one "head" of kv_latent_dim elements and no head stride.
+//
 // Memory-bound, one launch for K and V (blockIdx.y picks the operand).  A wave owns one
 // (sequence, row) at a time: length, row count and block-table entry are uniform loads on the
 // scalar path and the position, page and both base addresses are formed once per row; the lanes
@@ -112,11 +115,13 @@ __global__ __launch_bounds__(64 * kAppendWaves) void mfa_paged_append_kernel(Pag
   }
 }
 
-hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8,
+hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8, int operands,
                                  hipStream_t stream) {
-  // A workgroup per kAppendWaves rows up to 32768 workgroups, which then stride over the rest.
+  // A workgroup per kAppendWaves rows up to 32768 workgroups, which then stride over the rest;
+  // grid.y: the operands (key and value, or one latent pool).
   const int64_t wgs = (p.rows_total + kAppendWaves - 1) / kAppendWaves;
-  const dim3 grid((unsigned)std::min<int64_t>(wgs, 32768), 2, 1), block(64 * kAppendWaves);
+  const dim3 grid((unsigned)std::min<int64_t>(wgs, 32768), (unsigned)operands, 1),
+      block(64 * kAppendWaves);
   if (elem == P_FP16)
     return i8 ? launch(mfa_paged_append_kernel<F16, SRC_I8>, grid, block, 0, stream, p)
               : launch(mfa_paged_append_kernel<F16, SRC_SAME>, grid, block, 0, stream, p);

@@ -465,6 +465,77 @@ class PagedAppendDescriptor(ctypes.Structure):
         return d
 
 
+class PagedLatentCache(ctypes.Structure):
+    """mfa_paged_latent_cache_t: the MLA latent in fixed-size pages — one pool shared by every
+    head, a device block table and device sequence lengths (no reference counterpart)."""
+    _fields_ = [
+        ("pool", ctypes.c_void_p),
+        ("strides", ctypes.c_int64 * 2),
+        ("precision", ctypes.c_int32),
+        ("block_table", ctypes.c_void_p),
+        ("seq_lens", ctypes.c_void_p),
+        ("page_size", ctypes.c_uint32),
+        ("max_pages_per_seq", ctypes.c_uint32),
+        ("num_pages", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, precision, page_size, max_pages_per_seq, num_pages, latent_dim, pool=None,
+             block_table=None, seq_lens=None, strides=None):
+        """Pool [num_pages, page_size, latent_dim] unless `strides` (page, token slot; elements)
+        says otherwise.  Tensors may be None for a plan query."""
+        c = cls()
+        c.pool = _ptr(pool)
+        c.block_table, c.seq_lens = _ptr(block_table), _ptr(seq_lens)
+        if strides is None:
+            strides = (page_size * latent_dim, latent_dim)
+        c.strides = (ctypes.c_int64 * 2)(*[int(x) for x in strides])
+        c.precision = int(precision)
+        c.page_size, c.max_pages_per_seq, c.num_pages = page_size, max_pages_per_seq, num_pages
+        c._keep = (pool, block_table, seq_lens)  # the struct holds raw device pointers
+        return c
+
+
+class PagedMLADecodeDescriptor(ctypes.Structure):
+    """mfa_paged_mla_descriptor_t: R query rows per head over a paged latent cache."""
+    _fields_ = [
+        ("base", AttentionDescriptor),
+        ("batch_size", ctypes.c_uint32),
+        ("num_heads", ctypes.c_uint32),
+        ("rows", ctypes.c_uint32),
+        ("head_dim", ctypes.c_uint32),
+        ("kv_latent_dim", ctypes.c_uint32),
+        ("max_seq_len", ctypes.c_uint32),
+        ("precision", ctypes.c_int32),
+    ]
+
+    @classmethod
+    def make(cls, base: AttentionDescriptor, B, H, R, D, latent_dim, max_seq_len, precision):
+        d = cls()
+        d.base = base
+        d.batch_size, d.num_heads, d.rows = B, H, R
+        d.head_dim, d.kv_latent_dim, d.max_seq_len = D, latent_dim, max_seq_len
+        d.precision = int(precision)
+        return d
+
+
+class PagedLatentAppendDescriptor(ctypes.Structure):
+    _fields_ = [
+        ("precision", ctypes.c_int32),
+        ("batch_size", ctypes.c_uint32),
+        ("rows", ctypes.c_uint32),
+        ("kv_latent_dim", ctypes.c_uint32),
+        ("max_seq_len", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, precision, B, R, latent_dim, max_seq_len):
+        d = cls()
+        d.precision = int(precision)
+        d.batch_size, d.rows, d.kv_latent_dim, d.max_seq_len = B, R, latent_dim, max_seq_len
+        return d
+
+
 def _sig(name, restype, argtypes):
     fn = getattr(lib, name, None)
     if fn is None:
@@ -527,6 +598,14 @@ _sig("mfa_paged_kv_append", ctypes.c_int,
       _P(PagedKVCache), _V])
 _sig("mfa_paged_kv_append_plan", ctypes.c_int,
      [_P(PagedAppendDescriptor), _P(PagedKVCache), _P(KernelPlan)])
+_sig("mfa_paged_mla_decode_forward", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _V, _V, _V, _P(PagedLatentCache), _V, _V, _V])
+_sig("mfa_paged_mla_decode_plan", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _P(PagedLatentCache), _P(KernelPlan)])
+_sig("mfa_paged_latent_append", ctypes.c_int,
+     [_P(PagedLatentAppendDescriptor), _V, _P(ctypes.c_int64), _V, _P(PagedLatentCache), _V])
+_sig("mfa_paged_latent_append_plan", ctypes.c_int,
+     [_P(PagedLatentAppendDescriptor), _P(PagedLatentCache), _P(KernelPlan)])
 _sig("mfa_quantize_workspace_size", ctypes.c_size_t,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32])
 _sig("mfa_quantize", ctypes.c_int,
@@ -757,7 +836,7 @@ class QuantizedAttention:
 
 
 def _paged_plan(fn, desc, cache) -> list[dict]:
-    """One of the three mfa_paged_*_plan queries: the launches as multihead_plan lists them."""
+    """One of the mfa_paged_*_plan queries: the launches as multihead_plan lists them."""
     out = KernelPlan()
     check(fn(ctypes.byref(desc), None if cache is None else ctypes.byref(cache), ctypes.byref(out)))
     return out.as_list()
@@ -821,6 +900,44 @@ def paged_kv_append_plan(desc: PagedAppendDescriptor,
     """mfa_paged_kv_append_plan: the kernel paged_kv_append launches (see multihead_plan);
     without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
     return _paged_plan(lib.mfa_paged_kv_append_plan, desc, cache)
+
+
+def paged_mla_decode_forward(desc: PagedMLADecodeDescriptor, query, w_k, w_v,
+                             cache: PagedLatentCache, output, logsumexp=None, stream=None):
+    """mfa_paged_mla_decode_forward: absorbed MLA over a paged, ragged latent cache.  query
+    [B, H, R, D] 16-bit, w_k / w_v [latent, H * D], output FP32 [B, H, R, D]; causal is the
+    KV-cache convention (row q sees keys j <= seq_lens[b] - R + q).  The lengths and the block
+    table stay on the device, so the call can be captured in a graph and replayed."""
+    check(lib.mfa_paged_mla_decode_forward(ctypes.byref(desc), _ptr(query), _ptr(w_k), _ptr(w_v),
+                                           ctypes.byref(cache), _ptr(output), _ptr(logsumexp),
+                                           _stream(stream)))
+
+
+def paged_mla_decode_plan(desc: PagedMLADecodeDescriptor,
+                          cache: Optional[PagedLatentCache] = None) -> list[dict]:
+    """mfa_paged_mla_decode_plan: the kernels paged_mla_decode_forward launches (see
+    multihead_plan); without a cache, one of 256-key pages.  Needs no GPU."""
+    return _paged_plan(lib.mfa_paged_mla_decode_plan, desc, cache)
+
+
+def paged_latent_append(desc: PagedLatentAppendDescriptor, latent, cache: PagedLatentCache,
+                        new_lens=None, latent_strides=None, stream=None):
+    """mfa_paged_latent_append: the new rows latent [B, R, latent] (16-bit) go to their slots in
+    the cache's pool; cache.seq_lens holds the lengths AFTER the append, new_lens (device int32
+    [B], optional) the rows of each sequence.  Strides (batch, row) default to the tensor's own, so
+    a slice of a wider projection output works as it is."""
+    if latent_strides is None and hasattr(latent, "stride"):
+        latent_strides = latent.stride()[:2]
+    s = None if latent_strides is None else (ctypes.c_int64 * 2)(*[int(x) for x in latent_strides])
+    check(lib.mfa_paged_latent_append(ctypes.byref(desc), _ptr(latent), s, _ptr(new_lens),
+                                      ctypes.byref(cache), _stream(stream)))
+
+
+def paged_latent_append_plan(desc: PagedLatentAppendDescriptor,
+                             cache: Optional[PagedLatentCache] = None) -> list[dict]:
+    """mfa_paged_latent_append_plan: the kernel paged_latent_append launches (see
+    multihead_plan); without a cache, one of 256-key pages.  Needs no GPU."""
+    return _paged_plan(lib.mfa_paged_latent_append_plan, desc, cache)
 
 
 def quantize(x, target: Precision, mode: QuantMode = QuantMode.tensorWise, rows=None, cols=None,
