@@ -27,6 +27,11 @@
 // Both kernels also take K/V stored in the 16-bit compute type (SRC_SAME: the default
 // MultiHeadAttention.forward on an FP16 / BF16 cache, routed here by launch_forward in
 // mfa_api.cpp): decode16_kv16 / decode32_kv16 below.
+// Every body serves a contiguous and a paged entry point (the PG policy below).  The 16-bit
+// bodies are functions; the INT8 / INT4 bodies are texts included inside the __global__
+// functions (why: see those files): decode16_quant_body.h in both 16-row kernels,
+// decode32_quant_body.h in the paged 32-row kernel.  The contiguous 32-row kernel still carries
+// its own copy of that body (DESIGN.md §3 "Paged decode": its timing gate was not met).
 #include "mfa_stage.h"
 #include "mfa_dispatch.h"
 
@@ -192,8 +197,8 @@ __device__ __forceinline__ float xgroup_sum(float x) {
                         __builtin_bit_cast(float, (unsigned)r[1]));
 }
 
-// End of a 32-row workgroup of the 16-bit source (the quantised kernels below carry the same
-// text in place): the 4 waves' partials meet in LDS ([4][32][DP] O, then [4][32]
+// End of a 32-row workgroup of the 16-bit source (the quantised body carries the same
+// text itself): the 4 waves' partials meet in LDS ([4][32][DP] O, then [4][32]
 // (m, l)) over the ring once every wave is done with it.  One split: 256 threads merge them
 // into O and L.  Several splits: they combine them into the workgroup's one partial per row (a
 // quarter of the partial traffic and merge work of a partial per wave), in the merge's
@@ -737,6 +742,12 @@ __device__ __forceinline__ void decode32_kv16(const DecodeParams& dp, const PG& 
 // Q is loaded in that order; the packed K rows land XOR-swizzled by 16-byte chunk); V^T
 // fragments come straight from the packed V tile (same swizzle) by ds_read_b64_tr_b4 and are
 // widened in registers the same way (the zero point raised by 8: the nibble encodes n - 8).
+//
+// The quantised body below is decode32_quant_body.h with ContiguousKv written out.  Including
+// that file here (`using PG = ContiguousKv; const PG pg{};` in front) compiles to within 6
+// instructions of this code, but two of five shapes missed the timing gate by less than the
+// session's noise, so this kernel keeps the previous commit's code object; a fix to either
+// text goes into both (DESIGN.md §3 "Paged decode", profiles/decode_paged_ab.txt part 5).
 template <class E, int DP, int SRC = SRC_I8>
 __global__ void __launch_bounds__(256, DP >= 256 ? 1 : 2) mfa_fwd_decode_kernel(DecodeParams dp) {
   if constexpr (SRC == SRC_SAME) {
@@ -1006,289 +1017,20 @@ __global__ void __launch_bounds__(256, DP >= 256 ? 1 : 2) mfa_fwd_decode_kernel(
   }
 }
 
-// The INT8 body above as a function of the addressing policy, for the paged entry point below
-// (only PagedKv, only SRC_I8 is instantiated).  The contiguous kernel keeps its body in place:
-// lifted into this function it compiled to different code, which measured 3-7 % slower at 64
-// rows per kv head (profiles/decode_paged_ab.txt, part 3).
-template <class E, int DP, int SRC, class PG>
-__device__ __forceinline__ void decode32_quant(const DecodeParams& dp, const PG& pg, char* smem) {
-  const FwdParams& p = dp.f;
-  constexpr bool I4 = SRC == SRC_I4;
-  static_assert(!(PG::paged && I4), "paged caches: 16-bit and INT8");
-  // INT4 keeps three tiles in flight (four ring slots in the INT8 ring's bytes: the packed
-  // tiles are half as large, and V is read from the packed tile too).
-  constexpr int BK = 32, NSLOT = SRC == SRC_I4 ? 4 : 2, ND = DP / 32;
-  constexpr int ROWB = DP;                  // INT8 compute tile: one byte per element
-  using T = Tile16<ROWB / 2>;               // [BK][ROWB bytes], 16-byte chunks XOR-swizzled
-  constexpr int TILEB = BK * ROWB;          // one K or V compute tile
-  constexpr int ROWBS = I4 ? DP / 2 : DP;   // bytes per stored row
-  constexpr int TILEBS = BK * ROWBS;        // one stored (DMA) tile
-  constexpr int NPC = TILEBS / 1024;        // 1-KiB DMA pieces per tile
-  constexpr int RP = 1024 / ROWBS;          // rows per piece
-  static_assert(NPC >= 1 && NPC <= 8, "decode tile geometry");
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int l32 = lane & 31, hh = lane >> 5;
-  // Per wave: NSLOT DMA slots (K at 2s·TILEBS, V after it): 4·TILEB in all for both.
-  constexpr int WREG = NSLOT * 2 * TILEBS;
-  static_assert(WREG == 4 * TILEB, "per-wave LDS region");
-  char* const ring = smem + wave * WREG;
-
-  const int split = blockIdx.x;
-  const int u = blockIdx.y + gridDim.y * blockIdx.z;    // (b·H_kv + kvh)·nrt + rt
-  const int rt = u % dp.nrt;
-  const int bk = u / dp.nrt;
-  const int kvh = bk % p.Hkv, b = bk / p.Hkv;
-  const float c = p.c_log2;
-  const int C = kv_len(p, pg, b);
-
-  // The lane's query row of this tile: row = g·R + q of kv head kvh's group (h = kvh + g·H_kv).
-  const int row = rt * 32 + l32;
-  const bool rvalid = row < dp.rows;
-  i16x8 qf[DP / 16];
-  // Causal: the lane's query index sees keys 0 .. qcol (the host caps C at R, past which no
-  // row sees a key; paged: the R rows are the sequence's last R keys).
-  const int qcol = rvalid ? row % p.R + (PG::paged ? C - p.R : 0) : 0x3fffffff;
-  // Sliding window (mask row > key + window): the lane's first visible key (host: skip_ok).
-  const int wlo = p.mask.window ? qcol - (int)min(p.mask.window_size, 0x3fffffffu) : -0x40000000;
-  {
-    const int g = rvalid ? row / p.R : 0, q = rvalid ? row % p.R : 0;
-    const int h = kvh + g * p.Hkv;
-    const uint16_t* qrow =
-        (const uint16_t*)p.q.ptr + (int64_t)b * p.q.sb + (int64_t)h * p.q.sh + (int64_t)q * p.q.ss;
-#pragma unroll
-    for (int s = 0; s < DP / 16; ++s) {
-      const int d0 = I4 ? 32 * (s >> 1) + 16 * hh + 8 * (s & 1) : 16 * s + 8 * hh;
-      i16x8 v = i16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (rvalid && d0 < p.D) v = *reinterpret_cast<const i16x8*>(qrow + d0);
-      qf[s] = I4 ? i4_order<E>(v) : v;
-    }
-  }
-
-  // Keys of this split: [k0, k1); this wave's tiles k0 + 32·(wave + 4i).
-  const int k0 = split * dp.chunk;
-  const int k1 = min(C, k0 + dp.chunk);
-  const int nt = k1 > k0 ? (k1 - k0 + BK - 1) / BK : 0;
-  // Paged bodies keep the tile bookkeeping on the scalar path (the wave id is uniform).
-  const int uwave = PG::paged ? __builtin_amdgcn_readfirstlane(wave) : wave;
-  const int mine = nt > uwave ? (nt - uwave + 3) / 4 : 0;
-  MFA_PAGE_QUEUE(BK)
-
-  // LDS-DMA of one 32-row tile: piece n holds rows n·RP .. n·RP + RP - 1 (Tile16 rows are
-  // contiguous); lane l lands at byte 16·l of it = row n·RP + l / CPR, physical chunk l % CPR,
-  // so it fetches logical chunk (l % CPR) ^ swz(row).  Rows past C and chunks past D read as
-  // zeros (range-checked descriptor per piece, out-of-row chunks out of range).
-  constexpr int CPR = ROWBS / 16;
-  constexpr int SH = I4 ? 1 : 0;  // element -> byte offsets
-  // Packed INT4 K rows: 16-byte chunk c of row r at physical chunk c ^ swz4(r), so the 8-byte
-  // fragment reads of a half-wave (32 rows, one chunk) spread over 16 slots (2-way at most).
-  auto swz4 = [](int r) {
-    if constexpr (CPR == 2) return (r >> 3) & 1;
-    else if constexpr (CPR == 4) return (r >> 2) & 3;
-    else return (((r >> 1) & 1) << 2) | ((r >> 2) & 3);
-  };
-  const int ssb = (int)(p.k.ss >> SH);
-  int poff[NPC], voff[NPC];
-#pragma unroll
-  for (int n = 0; n < NPC; ++n) {
-    const int r = n * RP + lane / CPR;
-    const int ch = I4 ? (lane % CPR) ^ swz4(r) : (lane % CPR) ^ T::swz(r);
-    poff[n] = ch * 16 < (p.D >> SH) ? r * ssb + ch * 16 : 0x40000000;
-    // V: the same chunk placement as K (INT4: the transposed 4-bit reads below).
-    voff[n] = ch * 16 < (p.D >> SH) ? r * ssb + ch * 16 : 0x40000000;
-  }
-  const char* khead = (const char*)p.k.ptr + kv_head_bytes(pg, kvh) +
-                      (PG::paged ? 0 : ((int64_t)b * p.k.sb + (int64_t)kvh * p.k.sh) >> SH);
-  const char* vhead = (const char*)p.v.ptr + kv_head_bytes(pg, kvh) +
-                      (PG::paged ? 0 : ((int64_t)b * p.v.sb + (int64_t)kvh * p.v.sh) >> SH);
-  const int kbytes = (int)((int64_t)(C - 1) * ssb + (p.D >> SH));
-  const int vbytes = (int)((int64_t)(C - 1) * (p.v.ss >> SH) + (p.D >> SH));
-  auto issue = [&](int i, int slot, int page) {
-    const int t = tile_key(i);
-    char* kdst = ring + slot * 2 * TILEBS;
-    int nk, nv;
-    const char* kp = kv_tile(pg, khead, page, t, C, ssb, p.D >> SH, kbytes, &nk);
-    // V rows share the K piece geometry when the row strides agree (host-checked).
-    const char* vp = kv_tile(pg, vhead, page, t, C, ssb, p.D >> SH, vbytes, &nv);
-#pragma unroll
-    for (int n = 0; n < NPC; ++n) lds_dma16(kp, nk, poff[n], kdst + n * 1024);
-#pragma unroll
-    for (int n = 0; n < NPC; ++n) lds_dma16(vp, nv, voff[n], kdst + TILEBS + n * 1024);
-  };
-  // ds_read_b64_tr_b8 lanes (see attention_fwd_i8.hip): in each 16-lane group, lane 2j supplies
-  // the row of key acc_row(j + 8s, hh) and receives column d0 + (lane & 15) of the 8 rows.
-  const int trj = (lane & 15) >> 1;
-  const int trg = (lane >> 4) & 1;
-  const int trow0 = acc_row(trj, hh), trow1 = acc_row(trj + 8, hh);
-  // INT4 V^T fragments by ds_read_b64_tr_b4: in each 16-lane group lane r supplies row r (16
-  // nibbles = 16 d's of one key) and receives nibble (lane & 15) of all 16 rows, i.e. d =
-  // dt·32 + l32 for 16 keys: nibbles 0-7 are k-step 0's fragment, 8-15 k-step 1's.  The rows
-  // are chosen so that, after nib_widen's slot order (FP16: slot j <- nibble pi(j), pi = 0 2 4 6
-  // 1 3 5 7; BF16: natural), slot j of k-step ks holds key acc_row(8·ks + j, hh), the key order
-  // of the packed P.
-  int v4off = 0, v4sw = 0;
-  if constexpr (I4) {
-    const int r = lane & 15;
-    constexpr int PINV[8] = {0, 4, 1, 5, 2, 6, 3, 7};  // pi^-1
-    const int jj = E::prec == P_FP16 ? PINV[r & 7] : (r & 7);
-    const int key = acc_row(8 * (r >> 3) + jj, hh);
-    v4off = key * ROWBS + 8 * ((lane >> 4) & 1);
-    v4sw = swz4(key);
-  }
-  const float zk = (float)(p.k.zp + (I4 ? 8 : 0)), zv = (float)(p.v.zp + (I4 ? 8 : 0));
-
-  f32x16 o[ND];
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt) o[dt] = zero16();
-  float m = -kFltMax, lh = 0.f;
-
-#pragma unroll
-  // (Paged: NSLOT = 2, so the prologue issues tile 0 and step i tile i + 1.)
-  for (int n = 0; n < NSLOT - 1; ++n)
-    if (mine > n) issue(n, n, pg0);
-  for (int i = 0; i < mine; ++i) {
-    const int slot = i % NSLOT;
-    if (i + NSLOT - 1 < mine) {
-      issue(i + NSLOT - 1, (i + NSLOT - 1) % NSLOT, pg1);
-      pg_advance(i);
-      __builtin_amdgcn_s_waitcnt(vm_wait((NSLOT - 1) * 2 * NPC));  // tile i landed
-    } else if (NSLOT >= 4 && i + 2 < mine) {
-      __builtin_amdgcn_s_waitcnt(vm_wait(4 * NPC));  // tiles i + 1, i + 2 still in flight
-    } else if (NSLOT >= 3 && i + 1 < mine) {
-      __builtin_amdgcn_s_waitcnt(vm_wait(2 * NPC));  // tile i + 1 still in flight
-    } else {
-      wait_vm();
-    }
-    const char* kt = ring + slot * 2 * TILEBS;
-    const char* vt = kt + TILEBS;
-    const int t = tile_key(i);
-
-    // S^T = K·Q^T: key l32 on the A operand's row, elements d = 16s + 8hh + j (INT4: the lane
-    // order above, two k-steps per 8-byte read of the packed row).
-    f32x16 sa[1];
-    sa[0] = zero16();
-    if constexpr (I4) {
-      const char* kp = ring + slot * 2 * TILEBS;
-#pragma unroll
-      for (int a = 0; a < DP / 32; ++a) {
-        const uint2 kb =
-            *reinterpret_cast<const uint2*>(kp + l32 * ROWBS + 16 * (a ^ swz4(l32)) + 8 * hh);
-        sa[0] = E::mma(nib_widen<E>(kb.x, zk), qf[2 * a], sa[0]);
-        sa[0] = E::mma(nib_widen<E>(kb.y, zk), qf[2 * a + 1], sa[0]);
-      }
-    } else {
-#pragma unroll
-      for (int st = 0; st < DP / 16; ++st) {
-        const uint2 kb = *reinterpret_cast<const uint2*>(kt + T::off(l32, st) + 8 * hh);
-        sa[0] = E::mma(widen_i8<E>(kb.x, kb.y, zk), qf[st], sa[0]);
-      }
-    }
-    if (t + BK > C || (p.mask.causal && t + BK - 1 > qcol) || t < wlo) {
-      // Keys past C, (causal) keys past the lane's query index and (window) keys below
-      // qcol - window: -inf (key offset acc_row(r, hh) within the tile).
-      const int last = p.mask.causal ? min(C - 1, qcol) : C - 1;
-      mask_outside<1>(sa, wlo - t - 4 * hh, last - t - 4 * hh, -__builtin_inff());
-    }
-    f32x16& s = sa[0];
-    float mx = s[0];
-#pragma unroll
-    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-    mx = cross_half_max(mx) * c;
-    if (__any(mx > m)) {
-      const float m_new = fmaxf(m, mx);
-      const float corr = __builtin_amdgcn_exp2f(m - m_new);
-      m = m_new;
-      lh *= corr;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= corr;
-    }
-    float rs = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c, -m));
-      s[r] = pv;
-      rs += pv;
-    }
-    lh += rs;
-    i16x8 pb[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pb[ks][j] = (short)E::from_f32(s[8 * ks + j]);
-    // O^T += V^T·P^T.
-    if constexpr (I4) {
-      const char* vp = ring + slot * 2 * TILEBS + TILEBS;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) {
-        const i32x2d w = __builtin_amdgcn_ds_read_tr4_b64_v2i32(
-            (__attribute__((address_space(3))) i32x2d*)(vp + v4off + 16 * (dt ^ v4sw)));
-        o[dt] = E::mma(nib_widen<E>((uint32_t)w[0], zv), pb[0], o[dt]);
-        o[dt] = E::mma(nib_widen<E>((uint32_t)w[1], zv), pb[1], o[dt]);
-      }
-    } else {
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) {
-        const int col = dt * 32 + 16 * trg + 8 * (lane & 1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const char* pa = vt + T::off(ks ? trow1 : trow0, col >> 4) + (col & 15);
-          const i32x2d w = __builtin_amdgcn_ds_read_tr8_b64_v2i32(
-              (__attribute__((address_space(3))) i32x2d*)pa);
-          o[dt] = E::mma(widen_i8<E>((uint32_t)w[0], (uint32_t)w[1], zv), pb[ks], o[dt]);
-        }
-      }
-    }
-  }
-
-  const float l = cross_half_sum(lh);
-  // The 4 waves' partials meet in LDS ([4][32][DP] O, then [4][32] (m, l)) over the ring once
-  // every wave is done with it.  One split: 256 threads merge them into O and L.  Several
-  // splits: they combine them into the workgroup's one partial per row (a quarter of the
-  // partial traffic and merge work of a partial per wave), in the merge's arithmetic, so the
-  // merge pass of a single split reproduces the in-workgroup result bit for bit.
-  __syncthreads();
-  float* po = reinterpret_cast<float*>(smem);
-  float2* pml = reinterpret_cast<float2*>(smem + 4 * 32 * DP * 4);
-  float* prow = po + (wave * 32 + l32) * DP;
-#pragma unroll
-  for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      *reinterpret_cast<float4*>(prow + dt * 32 + 8 * g + 4 * hh) =
-          make_float4(o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]);
-  if (hh == 0) pml[wave * 32 + l32] = make_float2(m, l);
-  __syncthreads();
-  constexpr int CH = DP / 4, RPI = 256 / CH;  // 16-byte chunks per row, rows per pass
-  const int ch = tid % CH;
-#pragma unroll
-  for (int k = 0; k < 32 / RPI; ++k) {
-    const int r = tid / CH + k * RPI;
-    const int qr = rt * 32 + r;
-    if (qr < dp.rows) {
-      if (dp.fused) {
-        const int g = qr / p.R, q = qr % p.R;
-        merge_partials(p, pml + r, 32, po + r * DP, 32 * DP, 4, b, kvh + g * p.Hkv, q, 4 * ch,
-                       ch == 0);
-      } else {
-        store_split_partial(p, dp, pml + r, 32, po + r * DP, 32 * DP, u, split, r, 4 * ch);
-      }
-    }
-  }
-}
-
-// The 32-row bodies over a paged, ragged cache (PagedKv): 16-bit or INT8 K/V.
+// The 32-row bodies over a paged, ragged cache (PagedKv): 16-bit or INT8 K/V.  The INT8 body
+// is included, not called: see decode32_quant_body.h.
 template <class E, int DP, int SRC>
 __global__ void __launch_bounds__(256, DP >= 256 ? 1 : 2)
     mfa_fwd_decode_paged_kernel(PagedDecodeParams pp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const PagedKvPolicy pg{pp.pg};
-  if constexpr (SRC == SRC_SAME)
-    decode32_kv16<E, DP>(pp.d, pg, smem);
-  else
-    decode32_quant<E, DP, SRC>(pp.d, pg, smem);
+  using PG = PagedKvPolicy;
+  const PG pg{pp.pg};
+  const DecodeParams& dp = pp.d;
+  if constexpr (SRC == SRC_SAME) {
+    decode32_kv16<E, DP>(dp, pg, smem);
+  } else {
+#include "decode32_quant_body.h"
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1308,6 +1050,7 @@ __global__ void __launch_bounds__(256, DP >= 256 ? 1 : 2)
 //     32·c + 16·(j >> 2) + 4·g + (j & 3) for r = 8·c + pi(j); INT8 ds_read_b64_tr_b8: lanes
 //     2j, 2j + 1 supply key 16·(j >> 2) + 4·g + (j & 3)), so the P fragments are the S
 //     registers as they lie.
+// The quantised body is decode16_quant_body.h, included by both kernels below.
 template <int DP, int SRC>
 constexpr int decode16_lds() {
   constexpr int tile = SRC == SRC_I4 ? 64 * (DP / 2) : SRC == SRC_SAME ? 32 * DP * 2 : 32 * DP;
@@ -1326,551 +1069,29 @@ constexpr int decode32_lds() {
 template <class E, int DP, int SRC>
 __global__ void __launch_bounds__(256, DP == 256 && SRC != SRC_I8 ? 1 : 2)
     mfa_fwd_decode16_kernel(DecodeParams dp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using PG = ContiguousKv;
+  const PG pg{};
   if constexpr (SRC == SRC_SAME) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    decode16_kv16<E, DP>(dp, ContiguousKv{}, smem);
+    decode16_kv16<E, DP>(dp, pg, smem);
   } else {
-    const FwdParams& p = dp.f;
-    constexpr bool I4 = SRC == SRC_I4;
-    // V ring slots: 3 (two tiles ahead); 2 at D = 256 (one ahead: two workgroups per CU).
-    constexpr int BK = I4 ? 64 : 32, NKB = BK / 16, NV = DP == 256 ? 2 : 3, NDT = DP / 32;
-    constexpr int NDB = DP / 16;
-    constexpr int SH = I4 ? 1 : 0;            // element -> byte offsets
-    constexpr int ROWBS = DP >> SH;           // stored bytes per row
-    constexpr int TILEBS = BK * ROWBS;        // one stored key tile
-    constexpr int NPV = TILEBS / 1024;        // V DMA pieces per tile
-    constexpr int RP = 1024 / ROWBS;          // rows per piece
-    constexpr int CPR = ROWBS / 16;           // 16-byte chunks per row
-    constexpr int KLB = ROWBS / 4;            // K bytes per lane per 16-key block
-    constexpr int NKL = KLB >= 16 ? KLB / 16 : 1;  // K loads per block (b128, or one b64)
-    constexpr int NI = NPV + NKB * NKL;       // vm operations per tile
-    static_assert(DP == 64 || DP == 128 || DP == 256, "decode16 widths");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int l16 = lane & 15, g = lane >> 4;
-    char* const ring = smem + wave * NV * TILEBS;
-
-    const int split = blockIdx.x;
-    const int u = blockIdx.y + gridDim.y * blockIdx.z;    // b·H_kv + kvh (one row tile)
-    const int kvh = u % p.Hkv, b = u / p.Hkv;
-    const float c = p.c_log2;
-
-    // Q^T fragments: lane (query l16, group g), k-step dt: d = g·DP/4 + 8·dt + (kI4Perm)[j].
-    const int row = l16;
-    const bool rvalid = row < dp.rows;
-    const int qcol = rvalid ? row % p.R : 0x3fffffff;
-    const int wlo = p.mask.window ? qcol - (int)min(p.mask.window_size, 0x3fffffffu) : -0x40000000;
-    i16x8 qf[NDT];
-    {
-      const int gq = rvalid ? row / p.R : 0, q = rvalid ? row % p.R : 0;
-      const int h = kvh + gq * p.Hkv;
-      const uint16_t* qrow =
-          (const uint16_t*)p.q.ptr + (int64_t)b * p.q.sb + (int64_t)h * p.q.sh + (int64_t)q * p.q.ss;
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        const int d0 = g * (DP / 4) + 8 * dt;
-        i16x8 v = i16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (rvalid && d0 < p.D) v = *reinterpret_cast<const i16x8*>(qrow + d0);
-        qf[dt] = I4 ? i4_order<E>(v) : v;
-      }
-    }
-
-    // Keys of this split: [k0, k1); this wave's tiles k0 + BK·(wave + 4i).
-    const int k0 = split * dp.chunk;
-    const int k1 = min(p.C, k0 + dp.chunk);
-    const int nt = k1 > k0 ? (k1 - k0 + BK - 1) / BK : 0;
-    const int mine = nt > wave ? (nt - wave + 3) / 4 : 0;
-
-    const int ssb = (int)(p.k.ss >> SH);
-    const char* khead = (const char*)p.k.ptr + (((int64_t)b * p.k.sb + (int64_t)kvh * p.k.sh) >> SH);
-    const char* vhead = (const char*)p.v.ptr + (((int64_t)b * p.v.sb + (int64_t)kvh * p.v.sh) >> SH);
-    const int kbytes = (int)((int64_t)(p.C - 1) * ssb + (p.D >> SH));
-    const int vbytes = (int)((int64_t)(p.C - 1) * (p.v.ss >> SH) + (p.D >> SH));
-    // K row offsets of the lane's 16-key blocks (bytes past D: out of range, read as 0).
-    const int kcol = g * KLB < (p.D >> SH) ? g * KLB : 0x40000000;
-    int koff[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) koff[kb] = (16 * kb + l16) * ssb + kcol;
-    // V chunk swizzle: the 16 (INT4) / 8 + 8 (INT8) rows one transposed read gathers into a
-    // 32-lane half spread over the banks (INT4: 2-way at most; INT8: conflict-free).
-    auto vsw = [](int r) {
-      if constexpr (I4 && CPR == 8) return ((r >> 1) & 1) | (((r >> 4) & 3) << 1);
-      else if constexpr (I4) return (r >> 4) & (CPR - 1);
-      else if constexpr (CPR == 16) return (r & 3) | (((r >> 2) & 1) << 2) | (((r >> 4) & 1) << 3);
-      else if constexpr (CPR == 8) return ((r >> 1) & 1) | (((r >> 2) & 1) << 1) | (((r >> 4) & 1) << 2);
-      else return ((r >> 2) & 1) | (((r >> 4) & 1) << 1);
-    };
-    // V DMA: piece n holds rows n·RP .. n·RP + RP - 1; lane l lands at physical chunk l % CPR of
-    // row n·RP + l / CPR and fetches logical chunk (l % CPR) ^ vsw(row).
-    int voff[NPV];
-#pragma unroll
-    for (int n = 0; n < NPV; ++n) {
-      const int r = n * RP + lane / CPR;
-      const int ch = (lane % CPR) ^ vsw(r);
-      voff[n] = ch * 16 < (p.D >> SH) ? r * ssb + ch * 16 : 0x40000000;
-    }
-    // Transposed V reads: the row this lane supplies, and its swizzle.
-    int vtrow, vtsw;
-    {
-      constexpr int PINV[8] = {0, 4, 1, 5, 2, 6, 3, 7};  // kI4Perm^-1
-      int key;
-      if constexpr (I4) {
-        const int j = E::prec == P_FP16 ? PINV[l16 & 7] : (l16 & 7);
-        key = 32 * (l16 >> 3) + 16 * (j >> 2) + 4 * g + (j & 3);
-      } else {
-        const int j = l16 >> 1;
-        key = 16 * (j >> 2) + 4 * g + (j & 3);
-      }
-      vtrow = key * ROWBS + (I4 ? 0 : 8 * (l16 & 1));
-      vtsw = vsw(key);
-    }
-    const float zk = (float)(p.k.zp + (I4 ? 8 : 0)), zv = (float)(p.v.zp + (I4 ? 8 : 0));
-
-    uint32_t ka[NKB][KLB / 4], kn[NKB][KLB / 4];
-#define DEC16_KLOAD(KR, TI)                                                                       \
-    {                                                                                              \
-      const int tb_ = (k0 + BK * (wave + 4 * (TI))) * ssb;                                         \
-      const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc(                        \
-          (void*)(khead + tb_), (short)0, max(kbytes - tb_, 0), 0x00020000);                       \
-      _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) {                                         \
-        if constexpr (KLB >= 16) {                                                                 \
-          _Pragma("unroll") for (int x = 0; x < NKL; ++x) {                                        \
-            const auto a_ = __builtin_amdgcn_raw_buffer_load_b128(rs_, koff[kb] + 16 * x, 0, 0);   \
-            KR[kb][4 * x] = a_[0]; KR[kb][4 * x + 1] = a_[1];                                      \
-            KR[kb][4 * x + 2] = a_[2]; KR[kb][4 * x + 3] = a_[3];                                  \
-          }                                                                                        \
-        } else {                                                                                   \
-          const auto a_ = __builtin_amdgcn_raw_buffer_load_b64(rs_, koff[kb], 0, 0);               \
-          KR[kb][0] = a_[0]; KR[kb][1] = a_[1];                                                    \
-        }                                                                                          \
-      }                                                                                            \
-    }
-    auto vissue = [&](int i) {
-      const int rv = (k0 + BK * (wave + 4 * i)) * ssb;
-      char* dst = ring + (i % NV) * TILEBS;
-#pragma unroll
-      for (int n = 0; n < NPV; ++n) lds_dma16(vhead + rv, max(vbytes - rv, 0), voff[n], dst + n * 1024);
-    };
-
-    f32x4 o[NDB];
-#pragma unroll
-    for (int db = 0; db < NDB; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -kFltMax, lh = 0.f;
-
-    // Issue order V(0) K(0) V(1), then per tile i: K(i + 1) V(i + 2): V(i) always precedes K(i),
-    // so one counted vmcnt wait for K(i) covers both.  Two slots (D = 256): K(0) V(0), then per
-    // tile K(i + 1) V(i + 1), and the wait is for V(i).
-#define DEC16_STEP(KC, KN, I)                                                                     \
-    {                                                                                              \
-      const int ii = (I);                                                                          \
-      if (ii + 1 < mine) DEC16_KLOAD(KN, ii + 1);                                                  \
-      if constexpr (NV == 2) {                                                                     \
-        if (ii + 1 < mine) {                                                                       \
-          vissue(ii + 1);                                                                          \
-          __builtin_amdgcn_s_waitcnt(vm_wait(NI));                                                 \
-        } else {                                                                                   \
-          __builtin_amdgcn_s_waitcnt(vm_wait(0));                                                  \
-        }                                                                                          \
-      } else if (ii + 2 < mine) {                                                                  \
-        vissue(ii + 2);                                                                            \
-        __builtin_amdgcn_s_waitcnt(vm_wait(NI + NPV));                                             \
-      } else if (ii + 1 < mine) {                                                                  \
-        __builtin_amdgcn_s_waitcnt(vm_wait(NI));                                                   \
-      } else {                                                                                     \
-        __builtin_amdgcn_s_waitcnt(vm_wait(0));                                                    \
-      }                                                                                            \
-      const char* vs = ring + (ii % NV) * TILEBS;                                                  \
-      const int t = k0 + BK * (wave + 4 * ii);                                                     \
-      f32x4 sc[NKB];                                                                               \
-      _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) {                                         \
-        sc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};                                                        \
-        _Pragma("unroll") for (int dt = 0; dt < NDT; ++dt) {                                       \
-          if constexpr (I4)                                                                        \
-            sc[kb] = mma16<E>(nib_widen<E>(KC[kb][dt], zk), qf[dt], sc[kb]);                       \
-          else                                                                                     \
-            sc[kb] = mma16<E>(widen_i8<E>(KC[kb][2 * dt], KC[kb][2 * dt + 1], zk), qf[dt], sc[kb]); \
-        }                                                                                          \
-      }                                                                                            \
-      if (t + BK > k1 || (p.mask.causal && t + BK - 1 > qcol) || t < wlo) {                       \
-        const int last = (p.mask.causal ? min(k1 - 1, qcol) : k1 - 1) - t, first = wlo - t;        \
-        _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb)                                         \
-          _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                          \
-            const int kk = 16 * kb + 4 * g + e;                                                    \
-            sc[kb][e] = kk > last || kk < first ? -__builtin_inff() : sc[kb][e];                   \
-          }                                                                                        \
-      }                                                                                            \
-      float mx = fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3]));                      \
-      _Pragma("unroll") for (int kb = 1; kb < NKB; ++kb)                                           \
-        _Pragma("unroll") for (int e = 0; e < 4; ++e) mx = fmaxf(mx, sc[kb][e]);                   \
-      mx = xgroup_max(mx) * c;                                                                     \
-      if (__any(mx > m)) {                                                                         \
-        const float m_new = fmaxf(m, mx);                                                          \
-        const float corr = __builtin_amdgcn_exp2f(m - m_new);                                      \
-        m = m_new;                                                                                 \
-        lh *= corr;                                                                                \
-        _Pragma("unroll") for (int db = 0; db < NDB; ++db) o[db] *= corr;                          \
-      }                                                                                            \
-      float rs = 0.f;                                                                              \
-      _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb)                                           \
-        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                            \
-          const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kb][e], c, -m));               \
-          sc[kb][e] = pv;                                                                          \
-          rs += pv;                                                                                \
-        }                                                                                          \
-      lh += rs;                                                                                    \
-      i16x8 pb[NKB / 2];                                                                           \
-      _Pragma("unroll") for (int cc = 0; cc < NKB / 2; ++cc)                                       \
-        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                            \
-          pb[cc][e] = (short)E::from_f32(sc[2 * cc][e]);                                           \
-          pb[cc][4 + e] = (short)E::from_f32(sc[2 * cc + 1][e]);                                   \
-        }                                                                                          \
-      _Pragma("unroll") for (int db = 0; db < NDB; ++db) {                                         \
-        if constexpr (I4) {                                                                        \
-          const i32x2d w = __builtin_amdgcn_ds_read_tr4_b64_v2i32(                                 \
-              (__attribute__((address_space(3))) i32x2d*)(vs + vtrow + 16 * ((db >> 1) ^ vtsw) +   \
-                                                          8 * (db & 1)));                          \
-          o[db] = mma16<E>(nib_widen<E>((uint32_t)w[0], zv), pb[0], o[db]);                        \
-          o[db] = mma16<E>(nib_widen<E>((uint32_t)w[1], zv), pb[NKB / 2 - 1], o[db]);              \
-        } else {                                                                                   \
-          const i32x2d w = __builtin_amdgcn_ds_read_tr8_b64_v2i32(                                 \
-              (__attribute__((address_space(3))) i32x2d*)(vs + vtrow + 16 * (db ^ vtsw)));         \
-          o[db] = mma16<E>(widen_i8<E>((uint32_t)w[0], (uint32_t)w[1], zv), pb[0], o[db]);         \
-        }                                                                                          \
-      }                                                                                            \
-    }
-
-    if (mine > 0) {
-      if constexpr (NV == 2) {
-        DEC16_KLOAD(ka, 0);
-        vissue(0);
-      } else {
-        vissue(0);
-        DEC16_KLOAD(ka, 0);
-      }
-    }
-    if (NV == 3 && mine > 1) vissue(1);
-    for (int i = 0; i < mine; i += 2) {
-      DEC16_STEP(ka, kn, i);
-      if (i + 1 < mine) DEC16_STEP(kn, ka, i + 1);
-    }
-#undef DEC16_STEP
-#undef DEC16_KLOAD
-
-    const float l = xgroup_sum(lh);
-    // The 4 waves' partials meet in LDS ([4][16][DP] O, then [4][16] (m, l)) over the ring; one
-    // split: 256 threads merge them; several: the workgroup's one partial per row (as above).
-    __syncthreads();
-    float* po = reinterpret_cast<float*>(smem);
-    float2* pml = reinterpret_cast<float2*>(smem + 4 * 16 * DP * 4);
-    float* prow = po + (wave * 16 + l16) * DP;
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-      *reinterpret_cast<float4*>(prow + 16 * db + 4 * g) =
-          make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);
-    if (g == 0) pml[wave * 16 + l16] = make_float2(m, l);
-    __syncthreads();
-    constexpr int CH = DP / 4, RPI = 256 / CH;  // 16-byte chunks per row, rows per pass
-    const int ch = tid % CH;
-#pragma unroll
-    for (int k = 0; k < 16 / RPI; ++k) {
-      const int r = tid / CH + k * RPI;
-      if (r < dp.rows) {
-        if (dp.fused) {
-          const int gq = r / p.R, q = r % p.R;
-          merge_partials(p, pml + r, 16, po + r * DP, 16 * DP, 4, b, kvh + gq * p.Hkv, q, 4 * ch,
-                         ch == 0);
-        } else {
-          store_split_partial(p, dp, pml + r, 16, po + r * DP, 16 * DP, u, split, r, 4 * ch);
-        }
-      }
-    }
+#include "decode16_quant_body.h"
   }
 }
 
-// The same for the 16-row form (lifted, the INT4 instantiation of the contiguous kernel measured
-// 4-6 % slower; it keeps its body in place).
-template <class E, int DP, int SRC, class PG>
-__device__ __forceinline__ void decode16_quant(const DecodeParams& dp, const PG& pg, char* smem) {
-  const FwdParams& p = dp.f;
-  constexpr bool I4 = SRC == SRC_I4;
-  static_assert(!(PG::paged && I4), "paged caches: 16-bit and INT8");
-  // V ring slots: 3 (two tiles ahead); 2 at D = 256 (one ahead: two workgroups per CU).
-  constexpr int BK = I4 ? 64 : 32, NKB = BK / 16, NV = DP == 256 ? 2 : 3, NDT = DP / 32;
-  constexpr int NDB = DP / 16;
-  constexpr int SH = I4 ? 1 : 0;            // element -> byte offsets
-  constexpr int ROWBS = DP >> SH;           // stored bytes per row
-  constexpr int TILEBS = BK * ROWBS;        // one stored key tile
-  constexpr int NPV = TILEBS / 1024;        // V DMA pieces per tile
-  constexpr int RP = 1024 / ROWBS;          // rows per piece
-  constexpr int CPR = ROWBS / 16;           // 16-byte chunks per row
-  constexpr int KLB = ROWBS / 4;            // K bytes per lane per 16-key block
-  constexpr int NKL = KLB >= 16 ? KLB / 16 : 1;  // K loads per block (b128, or one b64)
-  constexpr int NI = NPV + NKB * NKL;       // vm operations per tile
-  static_assert(DP == 64 || DP == 128 || DP == 256, "decode16 widths");
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int l16 = lane & 15, g = lane >> 4;
-  char* const ring = smem + wave * NV * TILEBS;
-
-  const int split = blockIdx.x;
-  const int u = blockIdx.y + gridDim.y * blockIdx.z;    // b·H_kv + kvh (one row tile)
-  const int kvh = u % p.Hkv, b = u / p.Hkv;
-  const float c = p.c_log2;
-  const int C = kv_len(p, pg, b);
-
-  // Q^T fragments: lane (query l16, group g), k-step dt: d = g·DP/4 + 8·dt + (kI4Perm)[j].
-  const int row = l16;
-  const bool rvalid = row < dp.rows;
-  const int qcol = rvalid ? row % p.R + (PG::paged ? C - p.R : 0) : 0x3fffffff;
-  const int wlo = p.mask.window ? qcol - (int)min(p.mask.window_size, 0x3fffffffu) : -0x40000000;
-  i16x8 qf[NDT];
-  {
-    const int gq = rvalid ? row / p.R : 0, q = rvalid ? row % p.R : 0;
-    const int h = kvh + gq * p.Hkv;
-    const uint16_t* qrow =
-        (const uint16_t*)p.q.ptr + (int64_t)b * p.q.sb + (int64_t)h * p.q.sh + (int64_t)q * p.q.ss;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-      const int d0 = g * (DP / 4) + 8 * dt;
-      i16x8 v = i16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (rvalid && d0 < p.D) v = *reinterpret_cast<const i16x8*>(qrow + d0);
-      qf[dt] = I4 ? i4_order<E>(v) : v;
-    }
-  }
-
-  // Keys of this split: [k0, k1); this wave's tiles k0 + BK·(wave + 4i).
-  const int k0 = split * dp.chunk;
-  const int k1 = min(C, k0 + dp.chunk);
-  const int nt = k1 > k0 ? (k1 - k0 + BK - 1) / BK : 0;
-  // Paged bodies keep the tile bookkeeping on the scalar path (the wave id is uniform).
-  const int uwave = PG::paged ? __builtin_amdgcn_readfirstlane(wave) : wave;
-  const int mine = nt > uwave ? (nt - uwave + 3) / 4 : 0;
-  MFA_PAGE_QUEUE(BK)
-
-  const int ssb = (int)(p.k.ss >> SH);
-  const char* khead = (const char*)p.k.ptr + kv_head_bytes(pg, kvh) +
-                      (PG::paged ? 0 : ((int64_t)b * p.k.sb + (int64_t)kvh * p.k.sh) >> SH);
-  const char* vhead = (const char*)p.v.ptr + kv_head_bytes(pg, kvh) +
-                      (PG::paged ? 0 : ((int64_t)b * p.v.sb + (int64_t)kvh * p.v.sh) >> SH);
-  const int kbytes = (int)((int64_t)(C - 1) * ssb + (p.D >> SH));
-  const int vbytes = (int)((int64_t)(C - 1) * (p.v.ss >> SH) + (p.D >> SH));
-  // K row offsets of the lane's 16-key blocks (bytes past D: out of range, read as 0).
-  const int kcol = g * KLB < (p.D >> SH) ? g * KLB : 0x40000000;
-  int koff[NKB];
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) koff[kb] = (16 * kb + l16) * ssb + kcol;
-  // V chunk swizzle: the 16 (INT4) / 8 + 8 (INT8) rows one transposed read gathers into a
-  // 32-lane half spread over the banks (INT4: 2-way at most; INT8: conflict-free).
-  auto vsw = [](int r) {
-    if constexpr (I4 && CPR == 8) return ((r >> 1) & 1) | (((r >> 4) & 3) << 1);
-    else if constexpr (I4) return (r >> 4) & (CPR - 1);
-    else if constexpr (CPR == 16) return (r & 3) | (((r >> 2) & 1) << 2) | (((r >> 4) & 1) << 3);
-    else if constexpr (CPR == 8) return ((r >> 1) & 1) | (((r >> 2) & 1) << 1) | (((r >> 4) & 1) << 2);
-    else return ((r >> 2) & 1) | (((r >> 4) & 1) << 1);
-  };
-  // V DMA: piece n holds rows n·RP .. n·RP + RP - 1; lane l lands at physical chunk l % CPR of
-  // row n·RP + l / CPR and fetches logical chunk (l % CPR) ^ vsw(row).
-  int voff[NPV];
-#pragma unroll
-  for (int n = 0; n < NPV; ++n) {
-    const int r = n * RP + lane / CPR;
-    const int ch = (lane % CPR) ^ vsw(r);
-    voff[n] = ch * 16 < (p.D >> SH) ? r * ssb + ch * 16 : 0x40000000;
-  }
-  // Transposed V reads: the row this lane supplies, and its swizzle.
-  int vtrow, vtsw;
-  {
-    constexpr int PINV[8] = {0, 4, 1, 5, 2, 6, 3, 7};  // kI4Perm^-1
-    int key;
-    if constexpr (I4) {
-      const int j = E::prec == P_FP16 ? PINV[l16 & 7] : (l16 & 7);
-      key = 32 * (l16 >> 3) + 16 * (j >> 2) + 4 * g + (j & 3);
-    } else {
-      const int j = l16 >> 1;
-      key = 16 * (j >> 2) + 4 * g + (j & 3);
-    }
-    vtrow = key * ROWBS + (I4 ? 0 : 8 * (l16 & 1));
-    vtsw = vsw(key);
-  }
-  const float zk = (float)(p.k.zp + (I4 ? 8 : 0)), zv = (float)(p.v.zp + (I4 ? 8 : 0));
-
-  uint32_t ka[NKB][KLB / 4], kn[NKB][KLB / 4];
-#define DEC16_KLOAD(KR, TI, PAGE)                                                                 \
-  {                                                                                              \
-    int nb_;                                                                                     \
-    const char* tp_ =                                                                            \
-        kv_tile(pg, khead, PAGE, tile_key(TI), C, ssb, p.D >> SH, kbytes, &nb_);                 \
-    const __amdgpu_buffer_rsrc_t rs_ =                                                           \
-        __builtin_amdgcn_make_buffer_rsrc((void*)tp_, (short)0, nb_, 0x00020000);                \
-    _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) {                                         \
-      if constexpr (KLB >= 16) {                                                                 \
-        _Pragma("unroll") for (int x = 0; x < NKL; ++x) {                                        \
-          const auto a_ = __builtin_amdgcn_raw_buffer_load_b128(rs_, koff[kb] + 16 * x, 0, 0);   \
-          KR[kb][4 * x] = a_[0]; KR[kb][4 * x + 1] = a_[1];                                      \
-          KR[kb][4 * x + 2] = a_[2]; KR[kb][4 * x + 3] = a_[3];                                  \
-        }                                                                                        \
-      } else {                                                                                   \
-        const auto a_ = __builtin_amdgcn_raw_buffer_load_b64(rs_, koff[kb], 0, 0);               \
-        KR[kb][0] = a_[0]; KR[kb][1] = a_[1];                                                    \
-      }                                                                                          \
-    }                                                                                            \
-  }
-  auto vissue = [&](int i, int page) {
-    int nb;
-    const char* tp = kv_tile(pg, vhead, page, tile_key(i), C, ssb, p.D >> SH, vbytes, &nb);
-    char* dst = ring + (i % NV) * TILEBS;
-#pragma unroll
-    for (int n = 0; n < NPV; ++n) lds_dma16(tp, nb, voff[n], dst + n * 1024);
-  };
-
-  f32x4 o[NDB];
-#pragma unroll
-  for (int db = 0; db < NDB; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m = -kFltMax, lh = 0.f;
-
-  // Issue order V(0) K(0) V(1), then per tile i: K(i + 1) V(i + 2): V(i) always precedes K(i),
-  // so one counted vmcnt wait for K(i) covers both.  Two slots (D = 256): K(0) V(0), then per
-  // tile K(i + 1) V(i + 1), and the wait is for V(i).
-#define DEC16_STEP(KC, KN, I)                                                                     \
-  {                                                                                              \
-    const int ii = (I);                                                                          \
-    if (ii + 1 < mine) DEC16_KLOAD(KN, ii + 1, pg1);                                             \
-    if constexpr (NV == 2) {                                                                     \
-      if (ii + 1 < mine) {                                                                       \
-        vissue(ii + 1, pg1);                                                                     \
-        pg_advance(ii);                                                                          \
-        __builtin_amdgcn_s_waitcnt(vm_wait(NI));                                                 \
-      } else {                                                                                   \
-        __builtin_amdgcn_s_waitcnt(vm_wait(0));                                                  \
-      }                                                                                          \
-    } else if (ii + 2 < mine) {                                                                  \
-      vissue(ii + 2, pg2);                                                                       \
-      pg_advance(ii);                                                                            \
-      __builtin_amdgcn_s_waitcnt(vm_wait(NI + NPV));                                             \
-    } else if (ii + 1 < mine) {                                                                  \
-      __builtin_amdgcn_s_waitcnt(vm_wait(NI));                                                   \
-    } else {                                                                                     \
-      __builtin_amdgcn_s_waitcnt(vm_wait(0));                                                    \
-    }                                                                                            \
-    const char* vs = ring + (ii % NV) * TILEBS;                                                  \
-    const int t = tile_key(ii);                                                                  \
-    f32x4 sc[NKB];                                                                               \
-    _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) {                                         \
-      sc[kb] = f32x4{0.f, 0.f, 0.f, 0.f};                                                        \
-      _Pragma("unroll") for (int dt = 0; dt < NDT; ++dt) {                                       \
-        if constexpr (I4)                                                                        \
-          sc[kb] = mma16<E>(nib_widen<E>(KC[kb][dt], zk), qf[dt], sc[kb]);                       \
-        else                                                                                     \
-          sc[kb] = mma16<E>(widen_i8<E>(KC[kb][2 * dt], KC[kb][2 * dt + 1], zk), qf[dt], sc[kb]); \
-      }                                                                                          \
-    }                                                                                            \
-    if (t + BK > k1 || (p.mask.causal && t + BK - 1 > qcol) || t < wlo) {                       \
-      const int last = (p.mask.causal ? min(k1 - 1, qcol) : k1 - 1) - t, first = wlo - t;        \
-      _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb)                                         \
-        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                          \
-          const int kk = 16 * kb + 4 * g + e;                                                    \
-          sc[kb][e] = kk > last || kk < first ? -__builtin_inff() : sc[kb][e];                   \
-        }                                                                                        \
-    }                                                                                            \
-    float mx = fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3]));                      \
-    _Pragma("unroll") for (int kb = 1; kb < NKB; ++kb)                                           \
-      _Pragma("unroll") for (int e = 0; e < 4; ++e) mx = fmaxf(mx, sc[kb][e]);                   \
-    mx = xgroup_max(mx) * c;                                                                     \
-    if (__any(mx > m)) {                                                                         \
-      const float m_new = fmaxf(m, mx);                                                          \
-      const float corr = __builtin_amdgcn_exp2f(m - m_new);                                      \
-      m = m_new;                                                                                 \
-      lh *= corr;                                                                                \
-      _Pragma("unroll") for (int db = 0; db < NDB; ++db) o[db] *= corr;                          \
-    }                                                                                            \
-    float rs = 0.f;                                                                              \
-    _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb)                                           \
-      _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                            \
-        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kb][e], c, -m));               \
-        sc[kb][e] = pv;                                                                          \
-        rs += pv;                                                                                \
-      }                                                                                          \
-    lh += rs;                                                                                    \
-    i16x8 pb[NKB / 2];                                                                           \
-    _Pragma("unroll") for (int cc = 0; cc < NKB / 2; ++cc)                                       \
-      _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                            \
-        pb[cc][e] = (short)E::from_f32(sc[2 * cc][e]);                                           \
-        pb[cc][4 + e] = (short)E::from_f32(sc[2 * cc + 1][e]);                                   \
-      }                                                                                          \
-    _Pragma("unroll") for (int db = 0; db < NDB; ++db) {                                         \
-      if constexpr (I4) {                                                                        \
-        const i32x2d w = __builtin_amdgcn_ds_read_tr4_b64_v2i32(                                 \
-            (__attribute__((address_space(3))) i32x2d*)(vs + vtrow + 16 * ((db >> 1) ^ vtsw) +   \
-                                                        8 * (db & 1)));                          \
-        o[db] = mma16<E>(nib_widen<E>((uint32_t)w[0], zv), pb[0], o[db]);                        \
-        o[db] = mma16<E>(nib_widen<E>((uint32_t)w[1], zv), pb[NKB / 2 - 1], o[db]);              \
-      } else {                                                                                   \
-        const i32x2d w = __builtin_amdgcn_ds_read_tr8_b64_v2i32(                                 \
-            (__attribute__((address_space(3))) i32x2d*)(vs + vtrow + 16 * (db ^ vtsw)));         \
-        o[db] = mma16<E>(widen_i8<E>((uint32_t)w[0], (uint32_t)w[1], zv), pb[0], o[db]);         \
-      }                                                                                          \
-    }                                                                                            \
-  }
-
-  if (mine > 0) {
-    if constexpr (NV == 2) {
-      DEC16_KLOAD(ka, 0, pg0);
-      vissue(0, pg0);
-    } else {
-      vissue(0, pg0);
-      DEC16_KLOAD(ka, 0, pg0);
-    }
-  }
-  if (NV == 3 && mine > 1) vissue(1, pg1);
-  for (int i = 0; i < mine; i += 2) {
-    DEC16_STEP(ka, kn, i);
-    if (i + 1 < mine) DEC16_STEP(kn, ka, i + 1);
-  }
-#undef DEC16_STEP
-#undef DEC16_KLOAD
-
-  const float l = xgroup_sum(lh);
-  // The 4 waves' partials meet in LDS ([4][16][DP] O, then [4][16] (m, l)) over the ring; one
-  // split: 256 threads merge them; several: the workgroup's one partial per row (as above).
-  __syncthreads();
-  float* po = reinterpret_cast<float*>(smem);
-  float2* pml = reinterpret_cast<float2*>(smem + 4 * 16 * DP * 4);
-  float* prow = po + (wave * 16 + l16) * DP;
-#pragma unroll
-  for (int db = 0; db < NDB; ++db)
-    *reinterpret_cast<float4*>(prow + 16 * db + 4 * g) =
-        make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);
-  if (g == 0) pml[wave * 16 + l16] = make_float2(m, l);
-  __syncthreads();
-  constexpr int CH = DP / 4, RPI = 256 / CH;  // 16-byte chunks per row, rows per pass
-  const int ch = tid % CH;
-#pragma unroll
-  for (int k = 0; k < 16 / RPI; ++k) {
-    const int r = tid / CH + k * RPI;
-    if (r < dp.rows) {
-      if (dp.fused) {
-        const int gq = r / p.R, q = r % p.R;
-        merge_partials(p, pml + r, 16, po + r * DP, 16 * DP, 4, b, kvh + gq * p.Hkv, q, 4 * ch,
-                       ch == 0);
-      } else {
-        store_split_partial(p, dp, pml + r, 16, po + r * DP, 16 * DP, u, split, r, 4 * ch);
-      }
-    }
-  }
-}
-
+// The 16-row bodies over a paged, ragged cache.
 template <class E, int DP, int SRC>
 __global__ void __launch_bounds__(256, DP == 256 && SRC != SRC_I8 ? 1 : 2)
     mfa_fwd_decode16_paged_kernel(PagedDecodeParams pp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const PagedKvPolicy pg{pp.pg};
-  if constexpr (SRC == SRC_SAME)
-    decode16_kv16<E, DP>(pp.d, pg, smem);
-  else
-    decode16_quant<E, DP, SRC>(pp.d, pg, smem);
+  using PG = PagedKvPolicy;
+  const PG pg{pp.pg};
+  const DecodeParams& dp = pp.d;
+  if constexpr (SRC == SRC_SAME) {
+    decode16_kv16<E, DP>(dp, pg, smem);
+  } else {
+#include "decode16_quant_body.h"
+  }
 }
 
 // One query row per wave: combines the row's nsplit partials.  O is written with the

@@ -229,9 +229,9 @@ def test_bit_identical_to_contiguous_route(gpu, shape, C, monkeypatch):
         assert torch.equal(o, o0) and torch.equal(l, l0), shuffle
 
 
-def test_int8_bit_identical_to_contiguous_route(gpu):
-    B, H, Hkv, R, D, C, prec = 2, 4, 2, 8, 128, 2500, P.FP16
-    Q, Ks, Vs, quant, _, _ = problem(B, H, Hkv, R, D, prec, (C,) * B, kv8=True)
+def contiguous_int8(Q, quant, Hkv, C, prec):
+    """The quantised entry on the dense INT8 cache; returns (O, L, launched kernel names)."""
+    B, H, R, D = Q.shape
     base = mfa.AttentionDescriptor.make(R, C, D, low_precision_intermediates=True)
     desc = mfa.quantized_descriptor(base, prec, P.INT8, P.INT8, B=B, H=H, Hkv=Hkv)
     kq, vq = (torch.from_numpy(np.stack(q[0])).to(DEV) for q in quant)
@@ -243,10 +243,31 @@ def test_int8_bit_identical_to_contiguous_route(gpu):
         mfa.quantized_tensor(kq, P.INT8, scale=quant[0][1], zero_point=ZP),
         mfa.quantized_tensor(vq, P.INT8, scale=quant[1][1], zero_point=ZP), o0, l0)
     torch.cuda.synchronize()
-    names0 = [r["name"] for r in mfa.last_launches()]
+    return o0, l0, [r["name"] for r in mfa.last_launches()]
+
+
+def test_int8_bit_identical_to_contiguous_route(gpu):
+    B, H, Hkv, R, D, C, prec = 2, 4, 2, 8, 128, 2500, P.FP16
+    Q, Ks, Vs, quant, _, _ = problem(B, H, Hkv, R, D, prec, (C,) * B, kv8=True)
+    o0, l0, names0 = contiguous_int8(Q, quant, Hkv, C, prec)
     assert names0 == ["mfa_fwd_decode16_kernel<F16, 128, 1>", "mfa_decode_merge_kernel"], names0
     o, l, names = forward(Q, Cache(Ks, Vs, prec, 64, quant=quant), prec, C)
     assert names == ["mfa_fwd_decode16_paged_kernel<F16, 128, 1>", "mfa_decode_merge_kernel"], names
+    assert torch.equal(o, o0) and torch.equal(l, l0)
+
+
+@pytest.mark.parametrize("C", [2500, 300], ids=["split", "fused"])
+def test_int8_32row_bit_identical_to_contiguous_route(gpu, C):
+    # 20 rows per kv head: the 32-row form (the test above only reaches the 16-row one).
+    B, H, Hkv, R, D, prec = 2, 4, 1, 5, 128, P.FP16
+    Q, Ks, Vs, quant, _, _ = problem(B, H, Hkv, R, D, prec, (C,) * B, kv8=True)
+    o0, l0, names0 = contiguous_int8(Q, quant, Hkv, C, prec)
+    o, l, names = forward(Q, Cache(Ks, Vs, prec, 64, quant=quant), prec, C)
+    assert names0[0].startswith("mfa_fwd_decode_kernel<"), names0
+    assert names[0].startswith("mfa_fwd_decode_paged_kernel<"), names
+    assert names0[0].endswith(", 1>") and names[0].endswith(", 1>"), (names0, names)
+    assert names[1:] == names0[1:], (names, names0)
+    assert names[1:] == (["mfa_decode_merge_kernel"] if C == 2500 else []), names
     assert torch.equal(o, o0) and torch.equal(l, l0)
 
 
