@@ -715,6 +715,50 @@ mfa_status_t mfa_paged_mla_decode_plan(const mfa_paged_mla_descriptor_t* desc,
                                        const mfa_paged_latent_cache_t* cache,
                                        mfa_kernel_plan_t* out);
 
+/* The prompt side of that cache: mfa_paged_prefill_forward's semantics on the latent.  A ragged
+ * batch of chunks, each behind its own prefix, attends to the paged latent in one call, with no
+ * gather and no padding.  `desc` is the decode call's descriptor; rows is R, the rows per sequence
+ * in `query`, an upper bound when new_lens is given.  query: dense [B, H, R, D] in `precision`;
+ * w_k / w_v: [latent, H * D]; output: dense FP32 [B, H, R, D]; logsumexp: nullable [B, H, R], FP16
+ * when low_precision_intermediates, else FP32.
+ * Lengths: len_b = clamp(cache->seq_lens[b], 0, min(max_seq_len, max_pages_per_seq * page_size))
+ * is the length AFTER the chunk was appended, and n_b = new_lens ? clamp(new_lens[b], 0, R) : R
+ * (new_lens: device [B], nullable, never read by the host).  Row q < n_b of sequence b is key
+ * position t_q = len_b - n_b + q — the slot mfa_paged_latent_append wrote with the same cache,
+ * new_lens and rows.  MFA_SPARSITY_CAUSAL: row q attends to keys j <= t_q; MFA_SPARSITY_NONE:
+ * to keys 0 .. len_b - 1.  Sliding windows and sparse masks: MFA_ERR_UNSUPPORTED.
+ * Dead rows — q >= n_b, t_q < 0, every row when len_b == 0 — get output rows of exact zeros and
+ * L = -FLT_MAX in FP32, -inf in FP16; every row of output and logsumexp is written, for any
+ * device values, never with NaN.  The contents of query rows q >= n_b are never used: they may
+ * hold NaN or Inf.
+ * Safety: the decode call's — the table lookup is clamped to the sequence's row and page ids to
+ * [0, num_pages - 1]; no latent row at or past len_b is fetched, and table entries of pages no
+ * key lies in are never used.
+ * Supported: what mfa_paged_mla_decode_forward supports, checked by the same rules in the same
+ * order, with two limits of its own: B * H < 65536 for every shape, and
+ * B * ceil(H * R / 32) < 2^31.  batch_size == 0 or rows == 0 succeeds and launches nothing; the
+ * buffers may then be null.
+ * Three launches for any shape: Q * W_k^T by the batched general GEMM (also at R == 1, so a
+ * sequence alone and inside a batch project identically), the latent-space attention of 32-row
+ * query blocks over all of a block's keys, and the batched general GEMM with W_v into the FP32
+ * output.  Q * W_k^T and the latent-space output, 16-bit [B, H * R, latent] each, live in a
+ * library scratch slot of this call's own (mfa_release_scratch), sized by the descriptor alone.
+ * This call does not split the keys: a short chunk over a very long prefix (few rows, many keys)
+ * is mfa_paged_mla_decode_forward's shape.  Asynchronous on `stream`: no host read of device
+ * memory, no synchronisation; valid under stream capture after one warm-up call, so
+ * seq_lens += n, mfa_paged_latent_append and this call replay as one graph with new lengths and
+ * new_lens. */
+mfa_status_t mfa_paged_mla_prefill_forward(const mfa_paged_mla_descriptor_t* desc,
+                                           const void* query, const void* w_k, const void* w_v,
+                                           const int32_t* new_lens,
+                                           const mfa_paged_latent_cache_t* cache,
+                                           float* output, void* logsumexp, void* stream);
+/* The kernels that call launches (see mfa_multihead_plan).  cache == NULL plans a cache of
+ * 256-key pages in `precision`; NULL pointers inside a cache plan aligned buffers. */
+mfa_status_t mfa_paged_mla_prefill_plan(const mfa_paged_mla_descriptor_t* desc,
+                                        const mfa_paged_latent_cache_t* cache,
+                                        mfa_kernel_plan_t* out);
+
 typedef struct mfa_paged_latent_append_descriptor {
   int32_t precision;          /* MFA_PRECISION_FP16 / BF16: type of the new latent rows and the pool */
   uint32_t batch_size;

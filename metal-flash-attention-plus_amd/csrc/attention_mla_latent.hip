@@ -113,83 +113,10 @@ __global__ void __launch_bounds__(256, 2) mfa_mla_latent_kernel(LatentParams p) 
     if (has_next) load(t + BK);
     const char* kt = tb0 + cur * TILEB;
 
-    // Partial S^T over this wave's latent slice.
-    f32x16 sp = zero16();
-#pragma unroll
-    for (int ds = 0; ds < DS; ++ds)
-      sp = A::mma(A::read_row(kt, l32, wave * DS + ds, hh), qf[ds], sp);
-    // Exchange: each lane's 16 partial values contiguous ([wave][lane][16 floats]); the four
-    // 16-byte chunks are rotated by (lane >> 2) & 3 so the lanes of a ds_read_b128 group hit
-    // distinct banks.
-    const int xsw = (lane >> 2) & 3;
-    {
-      float* dst = xb + (wave * 64 + lane) * XST;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<f32x4*>(dst + 4 * (q ^ xsw)) =
-            f32x4{sp[4 * q], sp[4 * q + 1], sp[4 * q + 2], sp[4 * q + 3]};
-    }
-    __syncthreads();
-    f32x16 s;
-    {
-      f32x4 part[4][4];
-#pragma unroll
-      for (int w = 0; w < 4; ++w)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          part[w][q] = *reinterpret_cast<const f32x4*>(xb + (w * 64 + lane) * XST + 4 * (q ^ xsw));
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          s[4 * q + e] = ((part[0][q][e] + part[1][q][e]) + part[2][q][e]) + part[3][q][e];
-    }
-
-    if (t + BK > p.Skv || (p.causal && t + BK - 1 > spos)) {
-      MFA_KEEP_BRANCH();
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int key = t + acc_row(i, hh);
-        if (p.causal && key > spos) s[i] = kMaskValue;
-        if (key >= p.Skv) s[i] = -__builtin_inff();
-      }
-    }
-    float mx = s[0];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
-    const float m_tile = cross_half_max(mx) * c;
-    if (m_tile > m) {
-      const float corr = __builtin_amdgcn_exp2f(m - m_tile);
-      m = m_tile;
-      lh *= corr;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[dt][i] *= corr;
-    }
-    float rs = 0.f;
-    if (m < kMaskLevel) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        s[i] = __builtin_amdgcn_exp2f(mul_rn(s[i], c) - m);
-        rs += s[i];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        s[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, -m));
-        rs += s[i];
-      }
-    }
-    lh += rs;
-    // O^T += latent[:, slice]^T · P^T
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const i16x8 pb = A::pack(s, ks);
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
-        o[dt] = A::mma(A::read_tr(kt, 0, ks, wave * WS + 32 * dt, lane), pb, o[dt]);
-    }
+    // The tile's arithmetic, shared as text with the two paged kernels below.
+#define MLA_TILE_LEN p.Skv
+#define MLA_TILE_KLIM spos
+#include "mla_latent_tile_body.h"
     if (has_next) store(tb0 + (cur ^ 1) * TILEB);
     __syncthreads();
     cur ^= 1;
@@ -363,83 +290,9 @@ __global__ void __launch_bounds__(256, 2) mfa_mla_latent_paged_kernel(LatentPage
     ent_next = entry(t + 2 * BK);
     const char* kt = tb0 + cur * TILEB;
 
-    // Partial S^T over this wave's latent slice.
-    f32x16 sp = zero16();
-#pragma unroll
-    for (int ds = 0; ds < DS; ++ds)
-      sp = A::mma(A::read_row(kt, l32, wave * DS + ds, hh), qf[ds], sp);
-    // Exchange: each lane's 16 partial values contiguous ([wave][lane][16 floats]); the four
-    // 16-byte chunks are rotated by (lane >> 2) & 3 so the lanes of a ds_read_b128 group hit
-    // distinct banks.
-    const int xsw = (lane >> 2) & 3;
-    {
-      float* dst = xb + (wave * 64 + lane) * XST;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<f32x4*>(dst + 4 * (q ^ xsw)) =
-            f32x4{sp[4 * q], sp[4 * q + 1], sp[4 * q + 2], sp[4 * q + 3]};
-    }
-    __syncthreads();
-    f32x16 s;
-    {
-      f32x4 part[4][4];
-#pragma unroll
-      for (int w = 0; w < 4; ++w)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          part[w][q] = *reinterpret_cast<const f32x4*>(xb + (w * 64 + lane) * XST + 4 * (q ^ xsw));
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          s[4 * q + e] = ((part[0][q][e] + part[1][q][e]) + part[2][q][e]) + part[3][q][e];
-    }
-
-    if (t + BK > len || (p.causal && t + BK - 1 > klim)) {
-      MFA_KEEP_BRANCH();
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int key = t + acc_row(i, hh);
-        if (p.causal && key > klim) s[i] = kMaskValue;
-        if (key >= len) s[i] = -__builtin_inff();
-      }
-    }
-    float mx = s[0];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
-    const float m_tile = cross_half_max(mx) * c;
-    if (m_tile > m) {
-      const float corr = __builtin_amdgcn_exp2f(m - m_tile);
-      m = m_tile;
-      lh *= corr;
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[dt][i] *= corr;
-    }
-    float rs = 0.f;
-    if (m < kMaskLevel) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        s[i] = __builtin_amdgcn_exp2f(mul_rn(s[i], c) - m);
-        rs += s[i];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        s[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, -m));
-        rs += s[i];
-      }
-    }
-    lh += rs;
-    // O^T += latent[:, slice]^T · P^T
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const i16x8 pb = A::pack(s, ks);
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
-        o[dt] = A::mma(A::read_tr(kt, 0, ks, wave * WS + 32 * dt, lane), pb, o[dt]);
-    }
+#define MLA_TILE_LEN len
+#define MLA_TILE_KLIM klim
+#include "mla_latent_tile_body.h"
     if (has_next) store(tb0 + (cur ^ 1) * TILEB);
     __syncthreads();
     cur ^= 1;
@@ -464,6 +317,178 @@ __global__ void __launch_bounds__(256, 2) mfa_mla_latent_paged_kernel(LatentPage
       *reinterpret_cast<float4*>(op + dt * 32 + 8 * g + 4 * hh) =
           make_float4(o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]);
   if (wave == 0 && hh == 0) p.mlpart[prow] = make_float2(m, lp);
+}
+
+// Ragged prompt chunks over the paged latent cache (mfa_paged_mla_prefill_forward): the paged
+// kernel's staging and addressing, the dense kernel's non-split epilogue (l += FLT_MIN, Õ
+// normalised and rounded to E, L = m + log2 l), and rows that differ per sequence:
+//   * n_b = new_lens ? clamp(new_lens[b], 0, Sq) : Sq is a second scalar load; row q < n_b of a
+//     head's Sq rows is key position len_b − n_b + q, the slot the latent append wrote;
+//   * a row is live iff q < n_b and that position is >= 0; its limit klim is the position
+//     (causal) or len_b − 1 (unmasked), and a dead row carries klim = −1, so liveness costs no
+//     register of its own;
+//   * the Q̃ fragments of a dead row are zeros and are never loaded (the projection of an unused
+//     query row may be NaN); what the tile body makes of them is replaced at the store by zero Õ
+//     — the output GEMM then gives an exact-zero O row — and L at its floor;
+//   * the key loop ends at the largest limit among the block's live rows: the neighbours' smax
+//     logic with n_b − 1 in place of Sq − 1; a block with no live row has no key, so it loads no
+//     latent row and stores the dead result;
+//   * no split: one workgroup per 32-row block runs all of the block's keys.
+template <class E, int LAT>
+__global__ void __launch_bounds__(256, 2) mfa_mla_latent_prefill_kernel(LatentPrefillParams pp) {
+  constexpr int BK = 32, NT = 256;
+  constexpr int WS = LAT / 4;              // latent dims per wave
+  constexpr int DS = WS / 16;              // MFMA k-steps of the wave's QK^T slice
+  constexpr int ND = WS / 32;              // O^T tiles per wave
+  constexpr int CPR = LAT / 8;             // 16-byte chunks per latent row
+  constexpr int CPT = BK * CPR / NT;       // chunks staged per thread
+  constexpr int TILEB = BK * LAT * 2;
+  constexpr int XST = 16;                  // floats per lane in the exchange area
+  using A = Arith16<E, LAT>;
+  using TT = Tile16<LAT>;
+  const LatentParams& p = pp.c.l;
+  const PagedKv& pg = pp.c.pg;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const tb0 = smem;                              // 2 latent tiles
+  float* const xb = reinterpret_cast<float*>(smem + 2 * TILEB);  // [4 waves][64 lanes][XST]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int b = blockIdx.x / p.nblk;
+  const int r0 = (blockIdx.x % p.nblk) * 32;
+  const int r = r0 + l32;
+  const bool rvalid = r < p.R;
+
+  // The sequence's keys and rows (uniform), and the last key this row sees (-1: a dead row).
+  const int len = min(max(((latent_i32_ptr)pg.seq_lens)[b], 0), p.Skv);
+  const int nrow = pp.new_lens ? min(max(((latent_i32_ptr)pp.new_lens)[b], 0), p.Sq) : p.Sq;
+  const int first = len - nrow;             // key position of the head's row 0
+  int klim = -1;
+  {
+    const int spos = r % p.Sq;              // the row's index among its head's Sq rows
+    if (rvalid && spos < nrow && first + spos >= 0) klim = p.causal ? first + spos : len - 1;
+  }
+
+  // Keys this block needs: none without a live row (every wave holds the same 32 rows, so the
+  // vote is the workgroup's); else all of the sequence, or up to its live rows' largest limit.
+  int kend = 0;
+  if (__builtin_amdgcn_ballot_w64(klim >= 0) != 0) {
+    kend = len;
+    if (p.causal) {
+      const int rl = min(r0 + 31, p.R - 1);
+      const int smax = (r0 / p.Sq == rl / p.Sq) ? min(rl % p.Sq, nrow - 1) : nrow - 1;
+      kend = min(kend, first + smax + 1);
+    }
+  }
+
+  // Q̃ fragments of the wave's slice: d = w·WS + 16·ds + 8·hh + j.
+  i16x8 qf[DS];
+  {
+    const uint16_t* qrow = (const uint16_t*)p.q + ((int64_t)b * p.R + (rvalid ? r : 0)) * LAT;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) {
+      i16x8 v = i16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (klim >= 0) v = *reinterpret_cast<const i16x8*>(qrow + wave * WS + 16 * ds + 8 * hh);
+      qf[ds] = v;
+    }
+  }
+
+  // Block-table entry of the tile at key t (uniform), as stored; the lookup stays in the
+  // sequence's table row (the look-ahead runs past the last tile).
+  const latent_i32_ptr trow = (latent_i32_ptr)pg.block_table + (int64_t)b * pg.max_pages;
+  auto entry = [&](int t) { return trow[min(t >> pg.lg_page, pg.max_pages - 1)]; };
+  const int pmask = (1 << pg.lg_page) - 1;
+  // A tile is one buffer over its page rows below len_b (up to the last such row's end): a
+  // 16-byte load of a row at or past len_b lies outside it and returns zeros without a fetch.
+  // The token stride is below 2^24 bytes, so a tile's row offsets fit the 32-bit buffer offset.
+  const int tokb = (int)pp.c.tok_bytes;
+  const int voff0 = (tid / CPR) * tokb + 16 * (tid % CPR);   // chunk i: row tid / CPR + i·NT / CPR
+  const int vstep = (NT / CPR) * tokb;
+  uint4 stg[CPT];
+  auto load = [&](int t, int ent) {
+    const int page = min(max(ent, 0), pg.num_pages - 1);
+    const char* const base = (const char*)p.lat + (int64_t)page * pg.page_bytes +
+                             (int64_t)(t & pmask) * pp.c.tok_bytes;
+    const int nb = (min(len - t, BK) - 1) * tokb + LAT * 2;
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, nb, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < CPT; ++i)
+      stg[i] = __builtin_bit_cast(
+          uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff0 + i * vstep, 0, 0));
+  };
+  auto store = [&](char* tile) {
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int id = tid + NT * i;
+      *reinterpret_cast<uint4*>(tile + TT::off(id / CPR, id % CPR)) = stg[i];
+    }
+  };
+
+  f32x16 o[ND];
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt) o[dt] = zero16();
+  float m = -kFltMax, lh = 0.f;
+  const float c = p.c_log2;
+
+  int ent_next = 0;
+  if (0 < kend) {
+    load(0, entry(0));
+    store(tb0);
+    ent_next = entry(BK);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < kend; t += BK) {
+    const bool has_next = t + BK < kend;
+    if (has_next) load(t + BK, ent_next);
+    ent_next = entry(t + 2 * BK);
+    const char* kt = tb0 + cur * TILEB;
+
+#define MLA_TILE_LEN len
+#define MLA_TILE_KLIM klim
+#include "mla_latent_tile_body.h"
+    if (has_next) store(tb0 + (cur ^ 1) * TILEB);
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  float l = cross_half_sum(lh) + kFltMin;
+  if (!(l > 0.f)) l = kFltMin;
+  if (!rvalid) return;
+  const bool live = klim >= 0;
+  const float inv = 1.f / l;
+  uint16_t* orow = (uint16_t*)p.olat + ((int64_t)b * p.R + r) * LAT + wave * WS;
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d = dt * 32 + 8 * g + 4 * hh;
+      // The product rounded to FP32 and then to E, as the dense kernel's separate multiply and
+      // convert do: next to the select hipcc otherwise fuses the two into v_fma_mixlo_f16, one
+      // rounding of the exact product, and the two calls disagree at FP16 ties.
+      float x[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x[e] = o[dt][4 * g + e] * inv;
+        asm("" : "+v"(x[e]));
+      }
+      ushort4 v;
+      v.x = E::from_f32(x[0]);
+      v.y = E::from_f32(x[1]);
+      v.z = E::from_f32(x[2]);
+      v.w = E::from_f32(x[3]);
+      if (!live) v = make_ushort4(0, 0, 0, 0);
+      *reinterpret_cast<ushort4*>(orow + d) = v;
+    }
+  if (wave == 0 && hh == 0 && p.l) {
+    const float L = live ? m + __log2f(l) : -kFltMax;
+    const int64_t li = (int64_t)b * p.R + r;
+    if (p.l_f16)
+      reinterpret_cast<uint16_t*>(p.l)[li] = f32_to_f16(L);
+    else
+      reinterpret_cast<float*>(p.l)[li] = L;
+  }
 }
 
 // Merge of the key splits (flash-decoding): M = max m_s, w_s = exp2(m_s − M),
@@ -629,6 +654,16 @@ static hipError_t launch_latent_paged(const LatentPagedParams& p, hipStream_t st
   return launch(mfa_mla_latent_merge_kernel<E, LAT, 1>, dim3(l.B * l.R), dim3(MNT), 0, stream, l);
 }
 
+// The paged prefill: one launch, the latent-space output left in l.olat for the output GEMM.
+template <class E, int LAT>
+static hipError_t launch_latent_prefill(const LatentPrefillParams& p, hipStream_t stream) {
+  constexpr int LDS = 2 * 32 * LAT * 2 + 4 * 64 * 16 * 4;
+  const LatentParams& l = p.c.l;
+  if (!l.q || !l.olat || l.Sq < 1 || l.nblk < 1) return hipErrorInvalidValue;
+  return launch(mfa_mla_latent_prefill_kernel<E, LAT>, dim3(l.nblk * l.B), dim3(256), LDS, stream,
+                p);
+}
+
 // Decode query projection Q̃[b, h, :] = q[b, h, :] · W_k[:, h·D : (h+1)·D]ᵀ (S_q = 1): a workgroup
 // takes one head, QC latent columns and 32 batch rows; the W_k slice [QC][D] and the query rows
 // [32][D] sit in LDS (rows padded by 16 B), each thread accumulates QC/8 columns of one row in
@@ -727,6 +762,19 @@ hipError_t mla_latent_paged_dispatch(const LatentPagedParams& p, int elem, int l
   return hipErrorNotSupported;
 }
 
+hipError_t mla_latent_prefill_dispatch(const LatentPrefillParams& p, int elem, int lat,
+                                       hipStream_t stream) {
+  if (lat == 512 && elem == P_FP16) return launch_latent_prefill<F16, 512>(p, stream);
+  if (lat == 512 && elem == P_BF16) return launch_latent_prefill<BF16, 512>(p, stream);
+  if (lat == 256 && elem == P_FP16) return launch_latent_prefill<F16, 256>(p, stream);
+  if (lat == 256 && elem == P_BF16) return launch_latent_prefill<BF16, 256>(p, stream);
+  return hipErrorNotSupported;
+}
+
+template __global__ void mfa_mla_latent_prefill_kernel<F16, 512>(LatentPrefillParams);
+template __global__ void mfa_mla_latent_prefill_kernel<BF16, 512>(LatentPrefillParams);
+template __global__ void mfa_mla_latent_prefill_kernel<F16, 256>(LatentPrefillParams);
+template __global__ void mfa_mla_latent_prefill_kernel<BF16, 256>(LatentPrefillParams);
 template __global__ void mfa_mla_latent_paged_kernel<F16, 512>(LatentPagedParams);
 template __global__ void mfa_mla_latent_paged_kernel<BF16, 512>(LatentPagedParams);
 template __global__ void mfa_mla_latent_paged_kernel<F16, 256>(LatentPagedParams);

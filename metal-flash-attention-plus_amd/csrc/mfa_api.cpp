@@ -2250,15 +2250,13 @@ mfa_status_t paged_latent_plan(const Desc& d, const mfa_paged_latent_cache_t* ca
   return st;
 }
 
-// Absorbed MLA decode over the paged latent: Q̃ = Q·W_kᵀ (the dense call's launch for the
-// shape), mfa_mla_latent_paged_kernel over absorbed_layout's split at S_kv = cap, and the merge
-// that applies W_v — three launches for any split count.  Q̃ and the partials live in library
-// scratch slot 16, sized by the descriptor alone.
-mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void* query,
-                              const void* w_k, const void* w_v,
-                              const mfa_paged_latent_cache_t* cache, float* output,
-                              void* logsumexp, hipStream_t stream) {
-  const char* const what = "paged MLA decode";
+// The host rules of the two paged MLA calls, in their order, up to the empty call's exit: the
+// descriptor, the cache view, the masks, the scale and the grids.  Decode: the projection's grid
+// z is 32 batch rows per workgroup (R = 1, B > 1) or one (b, h) each; prefill: one (b, h) each
+// for every shape, and its B · ceil(H·R / 32) workgroups follow from B · H · R < 2^31.
+mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* desc,
+                            const mfa_paged_latent_cache_t* cache, bool prefill,
+                            PagedCacheView* cv, float* scale_out) {
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const mfa_attention_descriptor_t& base = desc->base;
   const int64_t B = desc->batch_size, H = desc->num_heads, R = desc->rows;
@@ -2272,9 +2270,8 @@ mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void
   if (Lat != 256 && Lat != 512)
     return fail(MFA_ERR_UNSUPPORTED, "%s: latent dimension %lld (256 or 512)", what,
                 (long long)Lat);
-  PagedCacheView cv;
   mfa_status_t st =
-      paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "descriptor's", &cv);
+      paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "descriptor's", cv);
   if (st != MFA_SUCCESS) return st;
   if (D % 8 != 0 || D > 256)
     return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of 8, at most 256)",
@@ -2288,16 +2285,46 @@ mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void
     return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
   if (B * H * R >= ((int64_t)1 << 31))
     return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
-  // The projection's grid z: 32 batch rows per workgroup (R = 1), or one (b, h) each.
-  if ((R == 1 && B > 1 ? (B + 31) / 32 : B * H) >= 65536)
+  if ((!prefill && R == 1 && B > 1 ? (B + 31) / 32 : B * H) >= 65536)
     return fail(MFA_ERR_UNSUPPORTED, "%s: %lld x %lld (batch, head) pairs exceed the grid", what,
                 (long long)B, (long long)H);
-  if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
-  if ((st = paged_latent_buffers(what, *cache, "query, w_k, w_v, output",
-                                 query && w_k && w_v && output)) != MFA_SUCCESS)
-    return st;
+  if (prefill && B * ((H * R + 31) / 32) >= ((int64_t)1 << 31))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: the query blocks exceed the grid", what);
+  *scale_out = scale;
+  return MFA_SUCCESS;
+}
+
+// ... and the buffers of a call that computes something.
+mfa_status_t paged_mla_buffers(const char* what, const mfa_paged_latent_cache_t& cache,
+                               const void* query, const void* w_k, const void* w_v,
+                               const void* output) {
+  const mfa_status_t st = paged_latent_buffers(what, cache, "query, w_k, w_v, output",
+                                               query && w_k && w_v && output);
+  if (st != MFA_SUCCESS) return st;
   if (!aligned16(query) || !aligned16(w_k) || !aligned16(w_v))
     return fail(MFA_ERR_UNSUPPORTED, "%s: query and weights must be 16-byte aligned", what);
+  return MFA_SUCCESS;
+}
+
+// Absorbed MLA decode over the paged latent: Q̃ = Q·W_kᵀ (the dense call's launch for the
+// shape), mfa_mla_latent_paged_kernel over absorbed_layout's split at S_kv = cap, and the merge
+// that applies W_v — three launches for any split count.  Q̃ and the partials live in library
+// scratch slot 16, sized by the descriptor alone.
+mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void* query,
+                              const void* w_k, const void* w_v,
+                              const mfa_paged_latent_cache_t* cache, float* output,
+                              void* logsumexp, hipStream_t stream) {
+  const char* const what = "paged MLA decode";
+  PagedCacheView cv;
+  float scale = 0.f;
+  mfa_status_t st = paged_mla_view(what, desc, cache, false, &cv, &scale);
+  if (st != MFA_SUCCESS) return st;
+  const mfa_attention_descriptor_t& base = desc->base;
+  const int64_t B = desc->batch_size, H = desc->num_heads, R = desc->rows;
+  const int64_t D = desc->head_dim, Lat = desc->kv_latent_dim;
+  const int prec = desc->precision;
+  if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
+  if ((st = paged_mla_buffers(what, *cache, query, w_k, w_v, output)) != MFA_SUCCESS) return st;
 
   const AbsorbedLayout al = absorbed_layout((int)B, (int)H, (int)R, (int)cv.cap, (int)Lat);
   if ((int64_t)al.nblk * B * al.nsplit >= ((int64_t)1 << 31))
@@ -2335,6 +2362,63 @@ mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void
   const hipError_t e = mfa::mla_latent_paged_dispatch(p, elem_of(prec), (int)Lat, stream);
   if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
   return hip_status(e, "paged MLA latent attention launch");
+}
+
+// The prompt side: ragged chunks behind their prefixes (paged_prefill's semantics on the
+// latent).  Three launches for every shape: Q̃ = Q·W_kᵀ by the general GEMM batched over (b, h)
+// — also at R = 1, so a sequence projects the same alone and in a batch —,
+// mfa_mla_latent_prefill_kernel over 32-row query blocks with no key split, and O = Õ·W_v by the
+// batched general GEMM into the FP32 output (a dead row's zero Õ gives an exact-zero O row).
+// Q̃ and Õ, 16-bit [B, H·R, Lat] each, live in library scratch slot 17, sized by the descriptor
+// alone.
+mfa_status_t paged_mla_prefill(const mfa_paged_mla_descriptor_t* desc, const void* query,
+                               const void* w_k, const void* w_v, const int32_t* new_lens,
+                               const mfa_paged_latent_cache_t* cache, float* output,
+                               void* logsumexp, hipStream_t stream) {
+  const char* const what = "paged MLA prefill";
+  PagedCacheView cv;
+  float scale = 0.f;
+  mfa_status_t st = paged_mla_view(what, desc, cache, true, &cv, &scale);
+  if (st != MFA_SUCCESS) return st;
+  const mfa_attention_descriptor_t& base = desc->base;
+  const int B = (int)desc->batch_size, H = (int)desc->num_heads, R = (int)desc->rows;
+  const int D = (int)desc->head_dim, Lat = (int)desc->kv_latent_dim;
+  const int prec = desc->precision;
+  if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
+  if ((st = paged_mla_buffers(what, *cache, query, w_k, w_v, output)) != MFA_SUCCESS) return st;
+
+  const size_t qbytes = ((size_t)B * H * R * Lat * 2 + 255) & ~(size_t)255;
+  void* ws = (void*)kPlanDummy;
+  if (!mfa::plan_capture() && (st = scratch(2 * qbytes, &ws, 17, stream)) != MFA_SUCCESS)
+    return st;
+  char* const qt = (char*)ws;
+  char* const ot = qt + qbytes;
+  // absorbed_project_query's launch for S_q > 1, for every R.
+  if ((st = absorbed_gemm(query, w_k, qt, R, Lat, D, D, Lat, 1, prec, prec, (int64_t)R * D,
+                          (int64_t)R * Lat, B * H, H, H, D, stream)) != MFA_SUCCESS)
+    return st;
+
+  mfa::LatentPrefillParams p;
+  memset(&p, 0, sizeof(p));
+  mfa::LatentParams& l = p.c.l;
+  l.q = qt;
+  l.lat = cache->pool;
+  l.olat = ot;
+  l.l = logsumexp;
+  l.l_f16 = resolve_precisions(base).mem[MFA_OPERAND_L] == MFA_PRECISION_FP16;
+  l.B = B; l.R = H * R; l.Sq = R; l.Skv = (int)cv.cap;
+  l.nblk = (H * R + 31) / 32;
+  l.c_log2 = 1.442695041f * scale;
+  l.causal = base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
+  p.c.pg = cv.pg;
+  p.c.tok_bytes = cache->strides[1] * cv.es;
+  p.new_lens = new_lens;
+  const hipError_t e = mfa::mla_latent_prefill_dispatch(p, elem_of(prec), Lat, stream);
+  if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
+  if ((st = hip_status(e, "paged MLA prefill latent attention launch")) != MFA_SUCCESS) return st;
+  // mfa_mla_forward_absorbed's output GEMM for B > 1, S_q > 1.
+  return absorbed_gemm(ot, w_v, output, R, D, Lat, Lat, D, 0, prec, MFA_PRECISION_FP32,
+                       (int64_t)R * Lat, (int64_t)R * D, B * H, H, H, D, stream);
 }
 
 // The write side: paged_append's kernel with one operand — one pool, one "head" of Lat
@@ -2463,6 +2547,26 @@ extern "C" mfa_status_t mfa_paged_mla_decode_plan(const mfa_paged_mla_descriptor
   const void* const vd = (const void*)kPlanDummy;
   return paged_latent_plan(*desc, cache, out, [&](const mfa_paged_latent_cache_t& c) {
     return paged_mla_decode(desc, vd, vd, vd, &c, (float*)kPlanDummy, nullptr, nullptr);
+  });
+}
+
+extern "C" mfa_status_t mfa_paged_mla_prefill_forward(const mfa_paged_mla_descriptor_t* desc,
+                                                      const void* query, const void* w_k,
+                                                      const void* w_v, const int32_t* new_lens,
+                                                      const mfa_paged_latent_cache_t* cache,
+                                                      float* output, void* logsumexp,
+                                                      void* stream) {
+  return paged_mla_prefill(desc, query, w_k, w_v, new_lens, cache, output, logsumexp,
+                           (hipStream_t)stream);
+}
+
+extern "C" mfa_status_t mfa_paged_mla_prefill_plan(const mfa_paged_mla_descriptor_t* desc,
+                                                   const mfa_paged_latent_cache_t* cache,
+                                                   mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  const void* const vd = (const void*)kPlanDummy;
+  return paged_latent_plan(*desc, cache, out, [&](const mfa_paged_latent_cache_t& c) {
+    return paged_mla_prefill(desc, vd, vd, vd, nullptr, &c, (float*)kPlanDummy, nullptr, nullptr);
   });
 }
 

@@ -116,6 +116,10 @@ hipError_t mla_latent_dispatch(const LatentParams& p, int elem, int lat, hipStre
 // split count (p.l.nsplit >= 1).
 hipError_t mla_latent_paged_dispatch(const LatentPagedParams& p, int elem, int lat,
                                      hipStream_t stream);
+// Ragged prompt chunks over that cache: one launch of 32-row query blocks, no key split, the
+// 16-bit latent-space output in p.c.l.olat (the caller applies W_v).
+hipError_t mla_latent_prefill_dispatch(const LatentPrefillParams& p, int elem, int lat,
+                                       hipStream_t stream);
 // Decode (S_q = 1) query projection of the absorbed MLA path; hipErrorNotSupported when the
 // shapes or alignment do not fit (the caller falls back to the general GEMM).
 hipError_t mla_qproj_dispatch(const void* q, const void* wk, void* qt, int B, int H, int D,

@@ -185,6 +185,14 @@ struct LatentPagedParams {
   int64_t tok_bytes;   // byte stride between the token slots of a page
 };
 
+// Ragged prompt chunks over the same cache (mfa_mla_latent_prefill_kernel): c.l.Sq is the rows
+// per head in the query, row q < n_b of batch item b at key position len_b - n_b + q.  No split:
+// c.l.olat is set, c.l.nsplit / chunk / opart / mlpart / wv / out are unused.
+struct LatentPrefillParams {
+  LatentPagedParams c;
+  const int32_t* new_lens;     // [B] rows of each sequence (clamped to [0, c.l.Sq]); NULL: c.l.Sq
+};
+
 // General GEMM (gemm_general.hip): any FP32/FP16/BF16 mix, transposes, leading dimensions.
 struct GemmGParams {
   const void* a;

@@ -602,6 +602,10 @@ _sig("mfa_paged_mla_decode_forward", ctypes.c_int,
      [_P(PagedMLADecodeDescriptor), _V, _V, _V, _P(PagedLatentCache), _V, _V, _V])
 _sig("mfa_paged_mla_decode_plan", ctypes.c_int,
      [_P(PagedMLADecodeDescriptor), _P(PagedLatentCache), _P(KernelPlan)])
+_sig("mfa_paged_mla_prefill_forward", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _V, _V, _V, _V, _P(PagedLatentCache), _V, _V, _V])
+_sig("mfa_paged_mla_prefill_plan", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _P(PagedLatentCache), _P(KernelPlan)])
 _sig("mfa_paged_latent_append", ctypes.c_int,
      [_P(PagedLatentAppendDescriptor), _V, _P(ctypes.c_int64), _V, _P(PagedLatentCache), _V])
 _sig("mfa_paged_latent_append_plan", ctypes.c_int,
@@ -918,6 +922,27 @@ def paged_mla_decode_plan(desc: PagedMLADecodeDescriptor,
     """mfa_paged_mla_decode_plan: the kernels paged_mla_decode_forward launches (see
     multihead_plan); without a cache, one of 256-key pages.  Needs no GPU."""
     return _paged_plan(lib.mfa_paged_mla_decode_plan, desc, cache)
+
+
+def paged_mla_prefill_forward(desc: PagedMLADecodeDescriptor, query, w_k, w_v,
+                              cache: PagedLatentCache, output, new_lens=None, logsumexp=None,
+                              stream=None):
+    """mfa_paged_mla_prefill_forward: a ragged batch of prompt chunks over a paged latent cache.
+    query [B, H, R, D] 16-bit (R = desc.rows, an upper bound with new_lens), w_k / w_v
+    [latent, H * D], output FP32 [B, H, R, D]; cache.seq_lens holds the lengths AFTER the chunks
+    were appended, new_lens (device int32 [B], optional) the rows of each sequence.  Row q < n_b is
+    key position seq_lens[b] - n_b + q; the other rows come back as zeros.  Nothing is read on the
+    host, so lens += n, paged_latent_append and this call can be captured in one graph."""
+    check(lib.mfa_paged_mla_prefill_forward(ctypes.byref(desc), _ptr(query), _ptr(w_k), _ptr(w_v),
+                                            _ptr(new_lens), ctypes.byref(cache), _ptr(output),
+                                            _ptr(logsumexp), _stream(stream)))
+
+
+def paged_mla_prefill_plan(desc: PagedMLADecodeDescriptor,
+                           cache: Optional[PagedLatentCache] = None) -> list[dict]:
+    """mfa_paged_mla_prefill_plan: the kernels paged_mla_prefill_forward launches (see
+    multihead_plan); without a cache, one of 256-key pages.  Needs no GPU."""
+    return _paged_plan(lib.mfa_paged_mla_prefill_plan, desc, cache)
 
 
 def paged_latent_append(desc: PagedLatentAppendDescriptor, latent, cache: PagedLatentCache,
