@@ -62,6 +62,47 @@ struct Tune {
 };
 using TuneDefault = Tune<>;
 
+// Instruction-count forms of the tile's building blocks ("lean"): same values,
+// fewer issued instructions.  A bit set in LN selects the lean form of one block; LN = 0 is the
+// earlier form, kept so that one process can A/B both and a test can compare them bit for bit
+// (MFA_DEV=1 MFA_FWD_LEAN=0, fwd_lean_off()).  Building with -DMFA_FWD_LEAN_DEFAULT=<bits> gives
+// a library with a subset for per-item A/B.
+enum : int {
+  LEAN_WAITS = 1,   // fwd2_qk / fwd2_pv: one counted lgkmcnt wait per pair of MFMAs
+  LEAN_MAX = 2,     // fwd2_max: IEEE maximum (no quieting of the MFMA results)
+  LEAN_SUMS = 4,    // fwd2_exp: the four partial row sums start from their first term
+  LEAN_FILL = 8,    // fwd2_tile: the PV chain's first reads go behind the last QK^T MFMA
+  LEAN_MASK1 = 32,  // fwd2_max: upper bound only where the caller has no window and no ranges
+};
+#ifndef MFA_FWD_LEAN_DEFAULT
+#define MFA_FWD_LEAN_DEFAULT (LEAN_WAITS | LEAN_MAX | LEAN_SUMS | LEAN_FILL | LEAN_MASK1)
+#endif
+constexpr int kFwdLean = MFA_FWD_LEAN_DEFAULT;
+
+// s_waitcnt lgkmcnt(n) alone (gfx9 encoding: vmcnt and expcnt left at their maxima).  The LDS
+// reads it counts are plain loads hipcc sees, so this only places a wait hipcc would otherwise
+// split over the following MFMAs; correctness never rests on the count.
+__device__ __forceinline__ void wait_lgkm(int n) {
+  switch (n) {
+    case 0: __builtin_amdgcn_s_waitcnt(0xC07F); break;
+    case 1: __builtin_amdgcn_s_waitcnt(0xC17F); break;
+    case 2: __builtin_amdgcn_s_waitcnt(0xC27F); break;
+    case 3: __builtin_amdgcn_s_waitcnt(0xC37F); break;
+    case 4: __builtin_amdgcn_s_waitcnt(0xC47F); break;
+    case 5: __builtin_amdgcn_s_waitcnt(0xC57F); break;
+    case 6: __builtin_amdgcn_s_waitcnt(0xC67F); break;
+    default: break;
+  }
+}
+// Fragments (of the read-ahead ring's AH, out of NM) that may stay in flight in front of MFMA
+// i when fragments i .. i + G - 1 must have landed: those issued so far (the first AH, then
+// one after each MFMA) less the ones needed.
+constexpr int lean_in_flight(int i, int AH, int G, int NM) {
+  const int issued = i + AH < NM ? i + AH : NM;
+  const int needed = i + G < NM ? i + G : NM;
+  return issued > needed ? issued - needed : 0;
+}
+
 // Per-wave running state of 32 query rows (one per lane, halves split the head dimension).
 template <int DP>
 struct RowState {
@@ -89,7 +130,7 @@ struct NoHook {
 // One tile in three parts: fwd2_qk (S^T = K·Q^T; S·c − moff on the fp16 path), fwd2_softmax
 // (masks, online softmax, P packed as the PV B operand) and fwd2_pv (O^T += V^T·P^T).
 // qk_hook(i) runs after QK^T MFMA i (e.g. staging the next tile piece by piece).
-template <class E, int DP, int BK, class TU = TuneDefault, class QKHook = NoHook>
+template <class E, int DP, int BK, class TU = TuneDefault, int LN = kFwdLean, class QKHook = NoHook>
 __device__ __forceinline__ void fwd2_qk(const char* kt, const int (&rbase)[2],
                                         const i16x8 (&qf)[DP / 16], const RowState<DP>& st,
                                         f32x16 (&s)[BK / 32], QKHook&& qk_hook = QKHook()) {
@@ -100,6 +141,8 @@ __device__ __forceinline__ void fwd2_qk(const char* kt, const int (&rbase)[2],
   constexpr int NJ = BK / 32, DS = DP / 16;
   constexpr int NM = DS * NJ;
   constexpr int AH = DP > 128 ? 2 : TU::AHK;
+  // Lean: one wait per G MFMAs (a ring of at least 4 keeps two fragments in flight behind it).
+  constexpr int G = (LN & LEAN_WAITS) && AH >= 4 ? 2 : 1;
   i16x8 kf[AH];
 #pragma unroll
   for (int i = 0; i < AH; ++i) kf[i] = A::read_row_a(kt, rbase, i % NJ, i / NJ);
@@ -107,6 +150,10 @@ __device__ __forceinline__ void fwd2_qk(const char* kt, const int (&rbase)[2],
 #pragma unroll
   for (int i = 0; i < NM; ++i) {
     const int ds = i / NJ, j = i % NJ;
+    if (G > 1 && i % G == 0) {
+      wait_lgkm(lean_in_flight(i, AH, G, NM));
+      if constexpr (TU::PIN) __builtin_amdgcn_sched_barrier(0);  // the wait stays in front
+    }
     if (ds == 0)
       s[j] = A::mma(kf[i % AH], qf[0], PS ? st.negm : zero16());
     else
@@ -122,7 +169,9 @@ __device__ __forceinline__ void fwd2_qk(const char* kt, const int (&rbase)[2],
 // beside another block's MFMAs: fwd2_max (edge / causal / window masks, row max, the lazy
 // rescale of O and l — a rarely taken branch) and fwd2_exp (P = exp2(S'), row sum, P packed
 // as the PV B operand; straight-line code).
-template <class E, int DP, int BK>
+// HI1: the caller has neither a window nor sparse ranges (rlo and rhi at their defaults), so a
+// masked tile has an upper bound only.
+template <class E, int DP, int BK, int LN = kFwdLean, bool HI1 = false>
 __device__ __forceinline__ void fwd2_max(RowState<DP>& st, f32x16 (&s)[BK / 32], int t,
                                          bool mask_tile, int qi, const FwdParams& p, float c,
                                          int wsz, int hh, int rlo = -0x40000000,
@@ -135,24 +184,39 @@ __device__ __forceinline__ void fwd2_max(RowState<DP>& st, f32x16 (&s)[BK / 32],
     // Keys t + 4hh + kk stay for lo <= kk <= hi: below C, at most qi (causal), at least
     // qi - wsz (window), inside the row's sparse range [rlo, rhi].
     const int base = t + 4 * hh;
-    int hi = min(p.C - 1, rhi) - base;
-    if (p.mask.causal) hi = min(hi, qi - base);
-    int lo = max(p.mask.window ? qi - wsz : -0x40000000, rlo);
-    lo = lo <= -0x40000000 ? -0x40000000 : lo - base;
-    mask_outside<NJ>(s, lo, hi, -__builtin_inff());
+    if constexpr (HI1 && (LN & LEAN_MASK1)) {
+      int hi = p.C - 1 - base;
+      if (p.mask.causal) hi = min(hi, qi - base);
+      mask_above<NJ>(s, hi, -__builtin_inff());
+    } else {
+      int hi = min(p.C - 1, rhi) - base;
+      if (p.mask.causal) hi = min(hi, qi - base);
+      int lo = max(p.mask.window ? qi - wsz : -0x40000000, rlo);
+      lo = lo <= -0x40000000 ? -0x40000000 : lo - base;
+      mask_outside<NJ>(s, lo, hi, -__builtin_inff());
+    }
   }
 
   float mx = s[0][0];
+  if constexpr (LN & LEAN_MAX) {
+    // MFMA results and -inf: never NaN.
 #pragma unroll
-  for (int j = 0; j < NJ; ++j)
+    for (int k = 1; k + 1 < 16 * NJ; k += 2)
+      mx = max3_nn(mx, s[k / 16][k % 16], s[(k + 1) / 16][(k + 1) % 16]);
+    mx = max_nn(mx, s[NJ - 1][15]);
+    mx = cross_half_maximum(mx);
+  } else {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) mx = fmaxf(mx, s[j][i]);
-  mx = cross_half_max(mx);
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) mx = fmaxf(mx, s[j][i]);
+    mx = cross_half_max(mx);
+  }
   // Tile max in absolute log2 units.
   const float mt = PS ? mx + st.moff : mx * c;
   if (__any(mt > st.m + THR)) {
     MFA_KEEP_BRANCH();
-    const float m_new = fmaxf(st.m, mt);
+    const float m_new = (LN & LEAN_MAX) ? max_nn(st.m, mt) : fmaxf(st.m, mt);
     const float corr = __builtin_amdgcn_exp2f(st.m - m_new);
     st.m = m_new;
     st.lh *= corr;
@@ -175,7 +239,7 @@ __device__ __forceinline__ void fwd2_max(RowState<DP>& st, f32x16 (&s)[BK / 32],
   }
 }
 
-template <class E, int DP, int BK>
+template <class E, int DP, int BK, int LN = kFwdLean>
 __device__ __forceinline__ void fwd2_exp(RowState<DP>& st, f32x16 (&s)[BK / 32],
                                          i16x8 (&pb)[BK / 16], float c) {
   using A = Arith16<E, DP>;
@@ -189,7 +253,11 @@ __device__ __forceinline__ void fwd2_exp(RowState<DP>& st, f32x16 (&s)[BK / 32],
       const float x = PS ? s[j][i] : __builtin_fmaf(s[j][i], c, -st.m);
       const float pv = __builtin_amdgcn_exp2f(x);
       s[j][i] = pv;
-      rs[i & 3] += pv;
+      // Lean: 0 + p is p for p >= +0, so the first term of each partial sum is stored.
+      if ((LN & LEAN_SUMS) && j == 0 && i < 4)
+        rs[i] = pv;
+      else
+        rs[i & 3] += pv;
     }
   st.lh += (rs[0] + rs[1]) + (rs[2] + rs[3]);
 #pragma unroll
@@ -198,33 +266,59 @@ __device__ __forceinline__ void fwd2_exp(RowState<DP>& st, f32x16 (&s)[BK / 32],
     for (int ks = 0; ks < 2; ++ks) pb[j * 2 + ks] = A::pack(s[j], ks);
 }
 
-template <class E, int DP, int BK>
+template <class E, int DP, int BK, int LN = kFwdLean, bool HI1 = false>
 __device__ __forceinline__ void fwd2_softmax(RowState<DP>& st, f32x16 (&s)[BK / 32],
                                              i16x8 (&pb)[BK / 16], int t, bool mask_tile, int qi,
                                              const FwdParams& p, float c, int wsz, int hh,
                                              int rlo = -0x40000000, int rhi = 0x3fffffff) {
-  fwd2_max<E, DP, BK>(st, s, t, mask_tile, qi, p, c, wsz, hh, rlo, rhi);
-  fwd2_exp<E, DP, BK>(st, s, pb, c);
+  fwd2_max<E, DP, BK, LN, HI1>(st, s, t, mask_tile, qi, p, c, wsz, hh, rlo, rhi);
+  fwd2_exp<E, DP, BK, LN>(st, s, pb, c);
 }
 
-template <class E, int DP, int BK, class TU = TuneDefault, class PVHook = NoHook>
-__device__ __forceinline__ void fwd2_pv(const char* vt, const int (&trb)[2],
-                                        const i16x8 (&pb)[BK / 16], RowState<DP>& st,
-                                        PVHook&& pv_hook = PVHook()) {
+// The PV chain's read-ahead ring.  Lean: a ring of AHV + 1 with one wait per two MFMAs keeps
+// every fragment's lead over its MFMA at least what the ring of AHV with a wait per MFMA gives
+// (two transposed reads per fragment).  D = 128 only: the ring's four more registers take the
+// D = 64 bf16 kernels from four waves per SIMD to three (128 -> 129-132 VGPRs), and D = 256
+// stands at the register limit.
+template <int DP, class TU, int LN>
+struct PvRing {
+  static constexpr bool LW = (LN & LEAN_WAITS) && DP == 128 && TU::AHV >= 3;
+  static constexpr int AH = DP > 128 ? 2 : TU::AHV + (LW ? 1 : 0);
+  static constexpr int G = LW ? 2 : 1;
+};
+
+// fwd2_pv in two parts: the ring's first AH fragment reads, [I0, I1) of them per call (they
+// depend on the V tile alone, so a caller may issue some before the softmax), and the chain.
+template <class E, int DP, int BK, class TU = TuneDefault, int LN = kFwdLean, int I0 = 0,
+          int I1 = PvRing<DP, TU, LN>::AH>
+__device__ __forceinline__ void fwd2_pv_head(const char* vt, const int (&trb)[2],
+                                             i16x8 (&vf)[PvRing<DP, TU, LN>::AH]) {
   using A = Arith16<E, DP>;
-  constexpr int NJ = BK / 32, ND = DP / 32;
-  constexpr int NM = NJ * 2 * ND;
-  constexpr int AH = DP > 128 ? 2 : TU::AHV;
-  i16x8 vf[AH];
+  constexpr int ND = DP / 32;
 #pragma unroll
-  for (int i = 0; i < AH; ++i) {
+  for (int i = I0; i < I1; ++i) {
     const int jk = i / ND, dt = i % ND;
     vf[i] = A::read_tr_a(vt, trb, (jk >> 1) * 32, jk & 1, dt * 32);
   }
+}
+
+template <class E, int DP, int BK, class TU = TuneDefault, int LN = kFwdLean, class PVHook = NoHook>
+__device__ __forceinline__ void fwd2_pv_chain(const char* vt, const int (&trb)[2],
+                                              i16x8 (&vf)[PvRing<DP, TU, LN>::AH],
+                                              const i16x8 (&pb)[BK / 16], RowState<DP>& st,
+                                              PVHook&& pv_hook = PVHook()) {
+  using A = Arith16<E, DP>;
+  constexpr int NJ = BK / 32, ND = DP / 32;
+  constexpr int NM = NJ * 2 * ND;
+  constexpr int AH = PvRing<DP, TU, LN>::AH, G = PvRing<DP, TU, LN>::G;
   if constexpr (TU::PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
   for (int i = 0; i < NM; ++i) {
     const int jk = i / ND, dt = i % ND;
+    if (G > 1 && i % G == 0) {
+      wait_lgkm(2 * lean_in_flight(i, AH, G, NM));
+      if constexpr (TU::PIN) __builtin_amdgcn_sched_barrier(0);
+    }
     st.o[dt] = A::mma(vf[i % AH], pb[jk], st.o[dt]);
     if (i + AH < NM) {
       const int jn = (i + AH) / ND, dn = (i + AH) % ND;
@@ -236,7 +330,17 @@ __device__ __forceinline__ void fwd2_pv(const char* vt, const int (&trb)[2],
   if constexpr (TU::PRIO) __builtin_amdgcn_s_setprio(0);
 }
 
-template <class E, int DP, int BK, class TU = TuneDefault, class QKHook = NoHook>
+template <class E, int DP, int BK, class TU = TuneDefault, int LN = kFwdLean, class PVHook = NoHook>
+__device__ __forceinline__ void fwd2_pv(const char* vt, const int (&trb)[2],
+                                        const i16x8 (&pb)[BK / 16], RowState<DP>& st,
+                                        PVHook&& pv_hook = PVHook()) {
+  i16x8 vf[PvRing<DP, TU, LN>::AH];
+  fwd2_pv_head<E, DP, BK, TU, LN>(vt, trb, vf);
+  fwd2_pv_chain<E, DP, BK, TU, LN>(vt, trb, vf, pb, st, pv_hook);
+}
+
+template <class E, int DP, int BK, class TU = TuneDefault, int LN = kFwdLean, bool HI1 = false,
+          class QKHook = NoHook>
 __device__ __forceinline__ void fwd2_tile(const char* kt, const char* vt, const int (&rbase)[2],
                                           const int (&trb)[2], const i16x8 (&qf)[DP / 16],
                                           RowState<DP>& st, int t, bool mask_tile, int qi,
@@ -245,9 +349,23 @@ __device__ __forceinline__ void fwd2_tile(const char* kt, const char* vt, const 
                                           int rhi = 0x3fffffff) {
   f32x16 s[BK / 32];
   i16x8 pb[BK / 16];
-  fwd2_qk<E, DP, BK, TU>(kt, rbase, qf, st, s, qk_hook);
-  fwd2_softmax<E, DP, BK>(st, s, pb, t, mask_tile, qi, p, c, wsz, hh, rlo, rhi);
-  fwd2_pv<E, DP, BK, TU>(vt, trb, pb, st);
+  fwd2_qk<E, DP, BK, TU, LN>(kt, rbase, qf, st, s, qk_hook);
+  // (D = 128 only, for its registers: see PvRing.)
+  if constexpr ((LN & LEAN_FILL) && DP == 128) {
+    // The V tile landed with the K tile (callers that let V land later run the three parts
+    // themselves), so the chain's first two fragment reads and their two address adds fill
+    // the wait states between the last QK^T MFMA and the first read of its result (the whole
+    // ring there costs 9 more registers at D = 128).
+    constexpr int AH = PvRing<DP, TU, LN>::AH, NPRE = AH < 2 ? AH : 2;
+    i16x8 vf[AH];
+    fwd2_pv_head<E, DP, BK, TU, LN, 0, NPRE>(vt, trb, vf);
+    fwd2_softmax<E, DP, BK, LN, HI1>(st, s, pb, t, mask_tile, qi, p, c, wsz, hh, rlo, rhi);
+    fwd2_pv_head<E, DP, BK, TU, LN, NPRE, AH>(vt, trb, vf);
+    fwd2_pv_chain<E, DP, BK, TU, LN>(vt, trb, vf, pb, st);
+  } else {
+    fwd2_softmax<E, DP, BK, LN, HI1>(st, s, pb, t, mask_tile, qi, p, c, wsz, hh, rlo, rhi);
+    fwd2_pv<E, DP, BK, TU, LN>(vt, trb, pb, st);
+  }
 }
 
 // Q fragments of the lane's query row, pre-scaled by c (rounded to the element type) on the

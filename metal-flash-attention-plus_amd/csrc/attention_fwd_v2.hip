@@ -74,8 +74,9 @@ __device__ __forceinline__ void fill_masked_rows(const FwdParams& p, int b, int 
 
 // ---------------------------------------------------------------------------------------
 // One 128-row query block per workgroup (4 waves x 32 rows); WPS workgroups' waves per SIMD.
-template <class E, int DP, int BK, int WPS, class TU = TuneDefault>
-__global__ void __launch_bounds__(256, WPS) mfa_fwd2_kernel(FwdParams p) {
+// LN: the forms of the tile's building blocks (attention_fwd2.h); the kernels follow the body.
+template <class E, int DP, int BK, class TU, int LN>
+__device__ __forceinline__ void fwd2_single_body(const FwdParams& p) {
   constexpr int NT = 256, BQ = 128;
   constexpr int TILEB = BK * DP * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -197,8 +198,8 @@ __global__ void __launch_bounds__(256, WPS) mfa_fwd2_kernel(FwdParams p) {
     };
     const bool mask_tile = (t + BK > p.C) || (p.mask.causal && t + BK - 1 > q0) ||
                            p.mask.window || t < in_lo || t + BK > in_hi;
-    fwd2_tile<E, DP, BK, TU>(kb0 + cur * TILEB, vb0 + cur * TILEB, rbase, trb, qf, st, t, mask_tile,
-                         qi, p, c, wsz, hh, hook, rlo, rhi);
+    fwd2_tile<E, DP, BK, TU, LN>(kb0 + cur * TILEB, vb0 + cur * TILEB, rbase, trb, qf, st, t,
+                                 mask_tile, qi, p, c, wsz, hh, hook, rlo, rhi);
     MFA_ACC(1);
     wait_vm();
     __syncthreads();
@@ -220,6 +221,16 @@ __global__ void __launch_bounds__(256, WPS) mfa_fwd2_kernel(FwdParams p) {
   MFA_CYC(1);
   MFA_STAMP_DRAIN();
   MFA_STAMP(4);
+}
+
+template <class E, int DP, int BK, int WPS, class TU = TuneDefault>
+__global__ void __launch_bounds__(256, WPS) mfa_fwd2_kernel(FwdParams p) {
+  fwd2_single_body<E, DP, BK, TU, kFwdLean>(p);
+}
+// The same kernel on the earlier forms of the building blocks (MFA_FWD_LEAN=0: A/B and tests).
+template <class E, int DP, int BK, int WPS>
+__global__ void __launch_bounds__(256, WPS) mfa_fwd2_plain_kernel(FwdParams p) {
+  fwd2_single_body<E, DP, BK, TuneDefault, 0>(p);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -469,9 +480,13 @@ __device__ __forceinline__ void share_widen2(char* img, const Kv8Geo<DP, BK>& ge
 // registers into their 16-bit slots (the shared tile by all 512 threads, a group's own tile by
 // its 256) and loads the bytes of the step after it (attention_fwd_kv8.hip's scheme, in this
 // schedule), so the MFMA operands are those of the dequantisation pass + 16-bit kernel path.
-template <class E, int DP, int BK, bool MIRROR, bool NTS, bool IMG, bool DV, int KVS>
+template <class E, int DP, int BK, bool MIRROR, bool NTS, bool IMG, bool DV, int KVS,
+          int LN = kFwdLean>
 __device__ __forceinline__ void fwd2_share_body(const FwdParams& p) {
   constexpr bool QKV = KVS != SRC_SAME;
+  // Mirrored pairs are causal-only (no window on this route, sparse ranges take the adjacent
+  // pairs): a masked tile has an upper bound only.
+  constexpr bool HI1 = MIRROR;
   static_assert(!(QKV && DV), "quantised K/V: no deferred-V prologue");
   constexpr int NT = 256, BQ = 128, ND = DP / 32;
   constexpr int TILEB = BK * DP * 2;
@@ -822,14 +837,14 @@ __device__ __forceinline__ void fwd2_share_body(const FwdParams& p) {
         constexpr int NPN = 2 * DmaA<DP, BK, 2 * NT>::PPW;
         f32x16 sc[BK / 32];
         i16x8 pb[BK / 16];
-        fwd2_qk<E, DP, BK>(kt, rbase, qf, st, sc);
-        fwd2_softmax<E, DP, BK>(st, sc, pb, tc, mask_tile, qi, p, c, wsz, hh);
+        fwd2_qk<E, DP, BK, TuneDefault, LN>(kt, rbase, qf, st, sc);
+        fwd2_softmax<E, DP, BK, LN, HI1>(st, sc, pb, tc, mask_tile, qi, p, c, wsz, hh);
         __builtin_amdgcn_s_waitcnt(0x0F70 | NPN);
         __syncthreads();
-        fwd2_pv<E, DP, BK>(vt, trb, pb, st);
+        fwd2_pv<E, DP, BK, TuneDefault, LN>(vt, trb, pb, st);
       } else {
-        fwd2_tile<E, DP, BK>(kt, vt, rbase, trb, qf, st, tc, mask_tile, qi, p, c, wsz, hh,
-                             NoHook(), rlo, rhi);
+        fwd2_tile<E, DP, BK, TuneDefault, LN, HI1>(kt, vt, rbase, trb, qf, st, tc, mask_tile, qi,
+                                                   p, c, wsz, hh, NoHook(), rlo, rhi);
       }
     }
     if constexpr (QKV) {
@@ -984,7 +999,7 @@ __device__ __forceinline__ bool fwd2_own_first_pair(const FwdParams& p) {
   return nA <= p.own_first && nB > nA;
 }
 
-template <class E, int DP, int BK, bool NTS>
+template <class E, int DP, int BK, bool NTS, int LN = kFwdLean>
 __device__ __forceinline__ void fwd2_share_own_first_body(const FwdParams& p) {
   constexpr int NT = 256, BQ = 128, ND = DP / 32;
   constexpr int TILEB = BK * DP * 2;
@@ -1135,17 +1150,18 @@ __device__ __forceinline__ void fwd2_share_own_first_body(const FwdParams& p) {
       f32x16 sc[BK / 32];
       i16x8 pb[BK / 16];
       if (have) {
-        fwd2_qk<E, DP, BK>(kt, rbase, qf, st, sc);
-        fwd2_softmax<E, DP, BK>(st, sc, pb, tc, mask_tile, qi, p, c, wsz, hh);
+        fwd2_qk<E, DP, BK, TuneDefault, LN>(kt, rbase, qf, st, sc);
+        fwd2_softmax<E, DP, BK, LN, true>(st, sc, pb, tc, mask_tile, qi, p, c, wsz, hh);
       }
       if (issued)
         __builtin_amdgcn_s_waitcnt(0x0F70 | NPN);
       else
         wait_vm();
       __syncthreads();
-      if (have) fwd2_pv<E, DP, BK>(vt, trb, pb, st);
+      if (have) fwd2_pv<E, DP, BK, TuneDefault, LN>(vt, trb, pb, st);
     } else if (have) {
-      fwd2_tile<E, DP, BK>(kt, vt, rbase, trb, qf, st, tc, mask_tile, qi, p, c, wsz, hh);
+      fwd2_tile<E, DP, BK, TuneDefault, LN, true>(kt, vt, rbase, trb, qf, st, tc, mask_tile, qi, p,
+                                                  c, wsz, hh);
     }
     wait_vm();
     __syncthreads();
@@ -1219,6 +1235,15 @@ __global__ void __launch_bounds__(512, 2) mfa_fwd2_share_kernel(FwdParams p) {
   }
   fwd2_share_body<E, DP, BK, MIRROR, NTS, IMG, DV, SRC_SAME>(p);
 }
+// The routed mirrored kernel on the earlier forms of the building blocks (MFA_FWD_LEAN=0).
+template <class E, int DP, int BK>
+__global__ void __launch_bounds__(512, 2) mfa_fwd2_share_plain_kernel(FwdParams p) {
+  if (fwd2_own_first_pair<BK>(p)) {
+    fwd2_share_own_first_body<E, DP, BK, true, 0>(p);
+    return;
+  }
+  fwd2_share_body<E, DP, BK, true, true, true, true, SRC_SAME, 0>(p);
+}
 
 constexpr int DP_KV8 = 128;
 
@@ -1259,6 +1284,15 @@ int fwd_own_first_tiles(bool mirrored, int kv_src, bool sparse_ranges) {
   return kFwdOwnFirstTiles;
 }
 
+// MFA_FWD_LEAN=0 (development A/B and tests): the routed mirrored kernel and the single-block
+// kernel run as mfa_fwd2_share_plain_kernel / mfa_fwd2_plain_kernel, on the earlier forms of the
+// tile's building blocks (attention_fwd2.h, LN = 0).  Every other kernel built on them has the
+// lean forms only.
+static bool fwd_lean_off() {
+  const char* e = mfa::dev_env("MFA_FWD_LEAN");
+  return e && e[0] == '0' && !e[1];
+}
+
 template <class E, int DP, int BK, bool MIRROR = true>
 static hipError_t launch_fwd2_share(const FwdParams& p, hipStream_t stream) {
   // Adjacent pairs use ring 0 only (every step is shared, no merge).
@@ -1287,12 +1321,17 @@ static hipError_t launch_fwd2_share(const FwdParams& p, hipStream_t stream) {
   // ... and A's O at the switch leaves through the wave's Q staging region as whole
   // half-rows (+0.8 % at C2; MFA_SHARE_SWI=0 keeps row-per-lane stores there).
   const char* swi = mfa::dev_env("MFA_SHARE_SWI");
-  if (MIRROR && !(dvv && dvv[0] == '0') && !(nt && nt[0] == '0')) {
-    if (swi && swi[0] == '0')
-      return launch(mfa_fwd2_share_kernel<E, DP, BK, MIRROR, true, false, true>,
+  if constexpr (MIRROR) {
+    if (!(dvv && dvv[0] == '0') && !(nt && nt[0] == '0')) {
+      if (swi && swi[0] == '0')
+        return launch(mfa_fwd2_share_kernel<E, DP, BK, MIRROR, true, false, true>,
+                      dim3(npairs * p.B * p.H), dim3(512), LDS, stream, q);
+      if (fwd_lean_off())
+        return launch(mfa_fwd2_share_plain_kernel<E, DP, BK>,
+                      dim3(npairs * p.B * p.H), dim3(512), LDS, stream, q);
+      return launch(mfa_fwd2_share_kernel<E, DP, BK, MIRROR, true, true, true>,
                     dim3(npairs * p.B * p.H), dim3(512), LDS, stream, q);
-    return launch(mfa_fwd2_share_kernel<E, DP, BK, MIRROR, true, true, true>,
-                  dim3(npairs * p.B * p.H), dim3(512), LDS, stream, q);
+    }
   }
   if constexpr (!MIRROR && LDS_IMG <= 160 * 1024) {
     // Adjacent pairs (D <= 128): both blocks leave through O row images by non-temporal
@@ -1313,7 +1352,9 @@ static hipError_t launch_fwd2_share(const FwdParams& p, hipStream_t stream) {
 template <class E, int DP, int BK, int WPS, class TU = TuneDefault>
 static hipError_t launch_fwd2(const FwdParams& p, hipStream_t stream) {
   constexpr int LDS = 4 * BK * DP * 2;
-  auto kern = mfa_fwd2_kernel<E, DP, BK, WPS, TU>;
+  auto kern = fwd_lean_off() && std::is_same<TU, TuneDefault>::value
+                  ? mfa_fwd2_plain_kernel<E, DP, BK, WPS>
+                  : mfa_fwd2_kernel<E, DP, BK, WPS, TU>;
   return launch(kern, dim3(p.nblk * p.B * p.H), dim3(256), LDS, stream, p);
 }
 

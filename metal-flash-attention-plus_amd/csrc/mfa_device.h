@@ -337,6 +337,31 @@ __device__ __forceinline__ void mask_outside(f32x16 (&s)[NJ], int lo, int hi, fl
     }
 }
 
+// mask_outside with no lower bound (causal and key-edge masks only): one compare and one
+// select per element.
+template <int NJ>
+__device__ __forceinline__ void mask_above(f32x16 (&s)[NJ], int hi, float val) {
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int kk = j * 32 + (i & 3) + 8 * (i >> 2);
+      s[j][i] = kk > hi ? val : s[j][i];
+    }
+}
+
+// Maximum of values that are never NaN (MFMA results, a running max, -inf).  fmaxf makes hipcc
+// quiet each MFMA result first (v_max_f32 x, x, x, one VALU per operand); the IEEE-754-2019
+// maximum needs no quieting, compiles to v_maximum3_f32, and gives the same bits for every
+// non-NaN input pair but (+0, -0), where it returns +0.  Plain C++, not an asm helper: an asm
+// statement reading an MFMA result gets none of the wait states that result needs.
+__device__ __forceinline__ float max_nn(float a, float b) {
+  return __builtin_elementwise_maximum(a, b);
+}
+__device__ __forceinline__ float max3_nn(float a, float b, float c) {
+  return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
+}
+
 // Max / sum across the two 32-lane halves (lanes l and l^32 hold the same column).
 __device__ __forceinline__ float xhalf_max(float x) { return fmaxf(x, __shfl_xor(x, 32)); }
 __device__ __forceinline__ float xhalf_sum(float x) { return x + __shfl_xor(x, 32); }
