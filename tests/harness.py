@@ -186,6 +186,215 @@ def assert_gradients_within_gate(got, ref, gate, rows=None, report=None):
         assert e[1] <= gate[name][1], f"{name} row error {e[1]:.3e} > gate {gate[name][1]:.3e}"
 
 
+# ------------------------------------------------------------------ forward: the key census
+# With Q = 0 every unmasked score is exactly 0, P is exactly 1 and every sum is a small integer
+# that FP32 holds exactly: a correct forward of any type gives 2^L = n (the number of keys the
+# row attends to) and n * O = the sum of those keys' V rows.  V holds small non-zero integers
+# in pairwise distinct rows, so one extra, missing or swapped key moves n or a column of the
+# sum by at least 1.  tests/test_forward_census.py proves on the CPU what this rejects.
+CENSUS_TOL = 0.25  # half the distance to the nearest wrong integer, with a factor of two to spare
+_MASK_VALUE = -(0.875 / 1.442695041) * 3.402823466e+38  # mfa_device.h:43, mfa_oracle.c
+
+
+def census_inputs(B, H, Hkv, R, C, D, seed):
+    """(Q, K, V) float32 for a key census: Q = 0, K Gaussian (a kernel that forgets a mask
+    meets arbitrary keys), V integers from {-2, -1, 1, 2} with pairwise distinct rows."""
+    rng = np.random.default_rng(seed)
+    Q = np.zeros((B, H, R, D), dtype=np.float32)
+    K = rng.standard_normal((B, Hkv, C, D)).astype(np.float32)
+    V = rng.choice(np.array([-2.0, -1.0, 1.0, 2.0], dtype=np.float32), size=(B, Hkv, C, D))
+    assert (V != 0).all()
+    for b in range(B):
+        for kv in range(Hkv):
+            assert len(np.unique(V[b, kv], axis=0)) == C, "census V rows must be distinct"
+    return Q, K, V
+
+
+def census_ranges(B, Hkv, R, C, seed):
+    """uint32 [B, Hkv, R, 2] key ranges in the manner of test_sparse_gpu.py's
+    test_ranges_beyond_sequence: different for every batch and kv head, some reaching past C,
+    some empty (x == y) and some with x > y."""
+    rng = np.random.default_rng(seed)
+    lo = rng.integers(0, C + 40, (B, Hkv, R))
+    hi = lo + rng.integers(-5, 200, (B, Hkv, R))
+    ranges = np.stack([lo, np.maximum(hi, 0)], -1).astype(np.uint32)
+    ranges[:, :, 5::11, 1] = ranges[:, :, 5::11, 0]      # empty rows
+    ranges[:, :, 2::7, 0] = ranges[:, :, 2::7, 0] // 4   # rows that start early
+    assert (ranges[..., 1] > C).any() and (ranges[..., 0] > ranges[..., 1]).any()
+    return ranges
+
+
+def assert_census(o, l, ok, V, ref_L):
+    """O [B, H, R, D] and L [B, H, R] (FP32 L, arrays or tensors) of a forward on
+    census_inputs against ok = allowed_keys(...) [B, H, R, C]; ref_L is the oracle's L.
+
+    Rows with n >= 1 allowed keys: rint(2^L) == n, |2^L - n| < CENSUS_TOL and
+    |rint(2^L) * O - sum of the allowed V rows| < CENSUS_TOL in every element.
+    Rows with none: the oracle's uniform average, |C * O - sum of all V rows| < CENSUS_TOL,
+    and L equal to the oracle's to rtol 1e-6.  Every row takes part (NaN fails)."""
+    o = o.detach().float().cpu().numpy() if isinstance(o, torch.Tensor) else np.asarray(o)
+    l = l.detach().float().cpu().numpy() if isinstance(l, torch.Tensor) else np.asarray(l)
+    o, l, V = o.astype(np.float64), l.astype(np.float64), np.asarray(V, dtype=np.float64)
+    B, H, R, C = ok.shape
+    Hkv = V.shape[1]
+    assert o.shape == (B, H, R, V.shape[3]) and l.shape == (B, H, R), (o.shape, l.shape)
+    n = ok.sum(axis=3)
+    live = n > 0
+    okf = ok.astype(np.float64)
+    want = np.stack([np.stack([okf[b, h] @ V[b, h % Hkv] for h in range(H)]) for b in range(B)])
+    with np.errstate(over="ignore", invalid="ignore"):
+        two = np.where(live, np.exp2(np.where(live, l, 0.0)), 0.0)
+    cnt = np.rint(two)
+    bad_n = live & ~((cnt == n) & (np.abs(two - n) < CENSUS_TOL))
+    with np.errstate(invalid="ignore"):
+        dev = np.abs(cnt[..., None] * o - want)
+    bad_o = live & ~(dev < CENSUS_TOL).all(axis=3)
+    for bad, what in ((bad_n, "key count"), (bad_o, "sum of V")):
+        if bad.any():
+            b, h, r = (int(x) for x in np.argwhere(bad)[0])
+            col = int(np.argmax(~(dev[b, h, r] < CENSUS_TOL)))
+            raise AssertionError(
+                f"census: {what} wrong in {int(bad.sum())} rows; first (b {b}, h {h}, row {r}): "
+                f"n {int(n[b, h, r])}, 2^L {two[b, h, r]:.6g}, rint(2^L) - n "
+                f"{cnt[b, h, r] - n[b, h, r]:.0f}, first differing column {col}: rint(2^L)*O "
+                f"{cnt[b, h, r] * o[b, h, r, col]:.6g} against {want[b, h, r, col]:.6g}")
+    dead = ~live
+    if dead.any():
+        allv = np.stack([np.stack([V[b, h % Hkv].sum(axis=0) for h in range(H)]) for b in range(B)])
+        with np.errstate(invalid="ignore"):
+            dd = np.abs(C * o - allv[:, :, None, :])
+        bad = dead & ~(dd < CENSUS_TOL).all(axis=3)
+        assert not bad.any(), (f"census: {int(bad.sum())} rows with no key are not the uniform "
+                               f"average; first (b, h, row) {np.argwhere(bad)[0]}")
+        assert np.allclose(l[dead], np.asarray(ref_L, dtype=np.float64)[dead], rtol=1e-6, atol=0)
+
+
+# ------------------------------------------------------------------ 16-bit forward gate
+# The forward's counterpart of the gradient gate: O is held to FWD_MARGIN x the error of
+# emulated_forward against the float64 reference on the case's own inputs, in the two metrics
+# of grad_errors; L to the same multiple of the emulation's max abs error plus the FP32 floor
+# below.  tests/test_forward_gate.py proves on the CPU what this rejects.
+FWD_MARGIN = 4.0
+# Relative (both O metrics): a case whose gate exceeds it is ill-conditioned, change its inputs.
+# Measured 4 x emulation over the cases of test_forward_gate.py and every gated GPU case: at
+# most 2.7e-3 (FP16) and 1.1e-2 (BF16; 2.5e-3 and 1e-2 on the six cases of the CPU proof alone).
+# The ceiling is twice the BF16 figure, rounded down.
+FWD_GATE_CEILING = 2e-2
+
+
+def _padded_d(D):
+    return 64 if D <= 64 else 128 if D <= 128 else 256
+
+
+def emulated_forward(Q, K, V, prec, causal=False, window=None, amask=None, ranges=None,
+                     scale=None, low_precision_intermediates=True, prescaled_q=False):
+    """The forward in numpy float64 on the kernel-visible inputs, rounded where the forward
+    kernels round and nowhere else:
+
+    * P = exp2(S*c - m) goes to the 16-bit type `prec` (round to nearest even) as the PV
+      operand, while the row sum l is taken from the unrounded FP32 P: the tuned kernels in
+      fwd2_exp (attention_fwd2.h:253-266: rs += pv, then A::pack), the generic kernel at
+      attention_fwd.hip:133-135 and :153; pack is E::from_f32 per element (mfa_device.h:228-231,
+      :53-61).  O = (P16 V) / l in FP32 (attention_fwd.hip:170).
+    * L = m + log2(l) goes to FP16 when low_precision_intermediates (store_l,
+      attention_fwd2.h:406-412; attention_fwd.hip:196-201).
+    * prescaled_q: the tuned FP16 kernels with a padded head width <= 128 round Q*c to FP16
+      before QK^T (prescale_q2, attention_fwd2.h:389-397, PS at :179/:246) and then take
+      S' = S - m from the MFMA directly.  BF16 and D = 256 keep Q and scale S in FP32
+      (attention_fwd2.h:253), and so does the generic kernel at any type (load_row_frags at
+      attention_fwd.hip:46, s*c - m at :133): pass prescaled_q=False for those.
+
+    Inputs stay exact and every sum is float64.  prec=None (or FP32) rounds nothing: the
+    float64 reference itself.  The additive mask is added to QK^T before scaling; rows with no
+    key allowed take the oracle's uniform P and its L = mask*c + log2 C.
+    Returns {"O": [B, H, R, D], "L": [B, H, R]} in float64."""
+    Q, K, V = (np.asarray(x, dtype=np.float64) for x in (Q, K, V))
+    B, H, R, D = Q.shape
+    Hkv, C = K.shape[1], K.shape[2]
+    kind = ROUND.get(prec)
+    sc = np.float32(1.0 / np.sqrt(np.float32(D))) if scale is None else np.float32(scale)
+    c2 = float(_LOG2E * sc)
+    ok = allowed_keys(B, H, Hkv, R, C, causal, window, ranges)
+    r16 = (lambda x, k: ol.round16(x.astype(np.float32), k).astype(np.float64))
+    prescaled_q = bool(prescaled_q and kind == "fp16" and _padded_d(D) <= 128 and D <= 256)
+    out = {"O": np.zeros((B, H, R, D)), "L": np.zeros((B, H, R))}
+    for b in range(B):
+        for h in range(H):
+            kv = h % Hkv
+            q, k, v, m = Q[b, h], K[b, kv], V[b, kv], ok[b, h]
+            if prescaled_q:
+                assert amask is None, "the pre-scaling kernels take no additive mask"
+                x = r16(q * c2, "fp16") @ k.T
+            else:
+                s = q @ k.T
+                if amask is not None:
+                    s = s + np.asarray(amask[b, h], dtype=np.float64)
+                x = c2 * s
+            x = np.where(m, x, -np.inf)
+            dead = ~m.any(axis=1)
+            x[dead] = 0.0
+            mx = x.max(axis=1, keepdims=True)
+            p = np.exp2(x - mx)
+            lsum = p.sum(axis=1)
+            L = mx[:, 0] + np.log2(lsum)
+            if kind:
+                p = r16(p, kind)
+                if low_precision_intermediates:
+                    L = np.where(dead, L, r16(L, "fp16"))
+            L = np.where(dead, float(np.float32(_MASK_VALUE)) * c2 + np.log2(C), L)
+            out["O"][b, h] = (p @ v) / lsum[:, None]
+            out["L"][b, h] = L
+    return out
+
+
+def forward_errors(got, ref):
+    """(slice error of O, row error of O, max abs error of L over the rows with a key) of
+    got = {"O", "L"} against ref; O in the metrics of grad_errors."""
+    lr = np.asarray(ref["L"], dtype=np.float64)
+    lg = np.asarray(got["L"], dtype=np.float64)
+    live = np.abs(lr) < 1e30
+    el = float(np.abs(lg - lr)[live].max()) if live.any() else 0.0
+    return (*grad_errors(got["O"], ref["O"]), el)
+
+
+def forward_gate(Qs, Ks, Vs, prec, ref, **kw):
+    """(slice gate of O, row gate of O, gate of L): FWD_MARGIN x the emulation's error against
+    `ref` (the float64 reference on the same kernel-visible inputs), computed from the reference
+    alone, never from what the GPU returned.  L also gets the FP32 floor D * 2^-24 * max|L|: the
+    kernels accumulate each score over D products in FP32 (forward error bound D * u of a dot
+    product, u = 2^-24, on scores of L's size), which the float64 emulation does not have;
+    it is 8e-5 at D 128 and |L| 10, next to a smallest L error of 2e-3 among the mutants."""
+    emu = emulated_forward(Qs, Ks, Vs, prec, **kw)
+    sl, rw, el = forward_errors(emu, ref)
+    # O's own FP32 floor, 8 ulps = 2^-21: O leaves as acc * (1 / l), a reciprocal and a product
+    # on top of the FP32 sums.  It matters only where the emulation is exact (a single key).
+    gate = (FWD_MARGIN * sl + 2.0 ** -21, FWD_MARGIN * rw + 2.0 ** -21)
+    assert max(gate) <= FWD_GATE_CEILING, (
+        f"O: gate {gate} over {FWD_GATE_CEILING}: ill-conditioned inputs")
+    lr = np.asarray(ref["L"], dtype=np.float64)
+    live = np.abs(lr) < 1e30
+    lmax = float(np.abs(lr[live]).max()) if live.any() else 0.0
+    return (*gate, FWD_MARGIN * el + Qs.shape[3] * 2.0 ** -24 * lmax)
+
+
+def prescales_q(names):
+    """Whether the launched kernels `names` (mfa.last_launches) are the tuned 16-bit forward
+    family built on attention_fwd2.h, which pre-scales an FP16 Q (emulated_forward decides on
+    the type and the padded width); the generic and big-D kernels never do."""
+    return any(n.startswith(("mfa_fwd2_", "mfa_fwd_pipe_")) for n in names)
+
+
+def assert_forward_within_gate(o, l, ref, gate, report=None):
+    """O (both metrics) and L of a forward (arrays or tensors) against `ref` under `gate`."""
+    cpu = lambda x: x.detach().float().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    e = forward_errors({"O": cpu(o), "L": cpu(l)}, ref)
+    print(f"fwd-gate {report or ''} O: slice {e[0]:.3e} (gate {gate[0]:.3e}) "
+          f"row {e[1]:.3e} (gate {gate[1]:.3e}) L: {e[2]:.3e} (gate {gate[2]:.3e})")
+    assert e[0] <= gate[0], f"O slice error {e[0]:.3e} > gate {gate[0]:.3e}"
+    assert e[1] <= gate[1], f"O row error {e[1]:.3e} > gate {gate[1]:.3e}"
+    assert e[2] <= gate[2], f"L error {e[2]:.3e} > gate {gate[2]:.3e}"
+
+
 def paged_cache(d, prec=None, page=64, **kw):
     """A PagedKVCache shaped for the paged decode, prefill or append descriptor d, of d's 16-bit
     type unless `prec` is given; its pointers are null (enough for a plan query)."""

@@ -6,6 +6,9 @@ Cases follow the reference's own tests (paths relative to the reference repo):
   - KernelRegressionTests: causal B1 H2 S96 D64 (tol 2e-3), pipeline-cache shapes S64/S80,
     strided BSHD == contiguous bit-exact, BF16 inputs 5e-3 (KernelRegressionTests.swift:238-512);
   - BASELINE.json config 1 (1 head fp32 S128 D64) and config 2 at full size on one head.
+
+Every FP16 / BF16 case of check_forward is also held to the forward gate of harness.py: O (slice
+and row metric) and L within 4 x the error of the rounding model on the case's own inputs.
 """
 import os
 
@@ -15,7 +18,8 @@ import torch
 
 import mfa_amd as mfa
 import oracle_lib as ol
-from harness import maxerr, relerr, run_forward, seen, to_device
+from harness import (assert_forward_within_gate, forward_gate, maxerr, prescales_q, relerr,
+                     run_forward, seen, to_device)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +31,23 @@ def gaussian(shape, seed):
 
 
 def check_forward(Qn, Kn, Vn, prec, tol_o, tol_l, **kw):
+    mfa.last_launches()
     o, l = run_forward(Qn, Kn, Vn, prec=prec, **kw)
-    ref = ol.attention(seen(Qn, prec), seen(Kn, prec), seen(Vn, prec),
-                       scale=kw.get("scale"), causal=kw.get("causal", False),
-                       window=kw.get("window"), amask=kw.get("amask"), ranges=kw.get("ranges"))
+    names = [r["name"] for r in mfa.last_launches()]
+    Qs, Ks, Vs = seen(Qn, prec), seen(Kn, prec), seen(Vn, prec)
+    masks = dict(scale=kw.get("scale"), causal=kw.get("causal", False), window=kw.get("window"),
+                 amask=kw.get("amask"), ranges=kw.get("ranges"))
+    ref = ol.attention(Qs, Ks, Vs, **masks)
     eo, el = maxerr(o, ref["O"]), maxerr(l, ref["L"])
     assert np.isfinite(o.cpu().numpy()).all()
     assert eo <= tol_o, f"O max error {eo} > {tol_o}"
     assert el <= tol_l, f"L max error {el} > {tol_l}"
+    if prec != FP32:
+        # The absolute bounds above are 5 to 50 % of O on unit Gaussians: every 16-bit case is
+        # also held to the rounding model's own error (harness.forward_gate).
+        gate = forward_gate(Qs, Ks, Vs, prec, ref, prescaled_q=prescales_q(names),
+                            low_precision_intermediates=l.dtype == torch.float16, **masks)
+        assert_forward_within_gate(o, l, ref, gate, report=f"{prec.name} {names}")
     return o, l, ref
 
 

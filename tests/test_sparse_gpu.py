@@ -6,7 +6,8 @@ half-open key range [x, y), indexed (b*H_kv + kv)*R + row; SparseMQABuilder.buil
 the key tiles outside the union of a query block's ranges; rows left with no unmasked key get
 the reference's finite-mask result (uniform average of V, L = mask*c + log2 C), written by the
 owning wave after the tile loop.  Tolerances: SquareAttentionTest.swift:557-571 (mixed O 5e-2); L here is kept in fp32
-(lowPrecisionIntermediates off) so the fully masked rows' L stays finite.
+(lowPrecisionIntermediates off) so the fully masked rows' L stays finite.  O and L are also held
+to the 16-bit forward gate of harness.py (4 x the rounding model's own error).
 """
 import numpy as np
 import pytest
@@ -14,7 +15,8 @@ import torch
 
 import mfa_amd as mfa
 import oracle_lib as ol
-from harness import maxerr, run_forward, seen
+from harness import (assert_forward_within_gate, forward_gate, maxerr, prescales_q, run_forward,
+                     seen)
 
 pytestmark = pytest.mark.gpu
 FP16, BF16 = mfa.Precision.FP16, mfa.Precision.BF16
@@ -51,8 +53,8 @@ def check(Q, K, V, prec, ranges, causal=False, window=None):
     o, l = run_forward(Q, K, V, prec=prec, causal=causal, window=window, ranges=ranges,
                        low_precision_intermediates=False)
     plan = [x["name"] for x in mfa.last_launches()]
-    ref = ol.attention(seen(Q, prec), seen(K, prec), seen(V, prec), causal=causal, window=window,
-                       ranges=ranges)
+    Qs, Ks, Vs = seen(Q, prec), seen(K, prec), seen(V, prec)
+    ref = ol.attention(Qs, Ks, Vs, causal=causal, window=window, ranges=ranges)
     on, ln = o.cpu().numpy(), l.float().cpu().numpy()
     assert np.isfinite(on).all()
     assert maxerr(on, ref["O"]) <= 5e-2
@@ -61,6 +63,12 @@ def check(Q, K, V, prec, ranges, causal=False, window=None):
     assert maxerr(ln[~big], ref["L"][~big]) <= 1e-2
     if big.any():
         assert np.allclose(ln[big], ref["L"][big], rtol=1e-6, atol=0)
+    # 5e-2 is 5 to 50 % of O: hold O (both metrics, every row) and L to the rounding model's own
+    # error as well.  Rows with no key are in both O metrics, against the oracle's uniform
+    # average; their L is held by the line above.
+    gate = forward_gate(Qs, Ks, Vs, prec, ref, prescaled_q=prescales_q(plan), causal=causal,
+                        window=window, ranges=ranges, low_precision_intermediates=False)
+    assert_forward_within_gate(on, ln, ref, gate, report=f"{prec.name} {plan}")
     return plan
 
 
