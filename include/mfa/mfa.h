@@ -622,7 +622,8 @@ typedef struct mfa_paged_prefill_descriptor {
  * unused slot (past len_b in its page) or of a page the table does not name for the keys read is
  * fetched.
  * Supported: pools of the query's type (FP16 or BF16) — INT8 and INT4 pools return
- * MFA_ERR_UNSUPPORTED (INT8 is the natural follow-up); D % 8 == 0, D <= 256; the cache struct by
+ * MFA_ERR_UNSUPPORTED (INT8 pools: mfa_quantized_paged_prefill_forward, below); D % 8 == 0,
+ * D <= 256; the cache struct by
  * the reader's rules (page size a power of two >= 32; strides >= 0 and multiples of 16 bytes;
  * token stride >= D and below 2^24 bytes; 16-byte aligned pools;
  * min(max_seq_len, max_pages_per_seq * page_size) <= 2^30; max_pages_per_seq * B < 2^31); a
@@ -641,6 +642,35 @@ mfa_status_t mfa_paged_prefill_forward(const mfa_paged_prefill_descriptor_t* des
  * 256-key pages; NULL pointers inside a cache plan aligned buffers. */
 mfa_status_t mfa_paged_prefill_plan(const mfa_paged_prefill_descriptor_t* desc,
                                     const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
+
+/* Paged prefill over a cache whose pools may be quantised: mfa_paged_prefill_forward's descriptor,
+ * arguments, lengths, masks, dead rows, safety rules and stream behaviour, with per-tensor INT8
+ * pools read as well — the prompt step of an INT8 cache, in stream order seq_lens += n ->
+ * mfa_paged_kv_append -> mfa_quantized_paged_prefill_forward (-> mfa_paged_decode_forward later),
+ * all on one `cache`.  It is to mfa_paged_prefill_forward what mfa_quantized_forward is to
+ * mfa_multihead_forward.
+ * INT8 pools are widened on load inside the kernel, with the decode call's folded scales: the
+ * MFMA operands are the exact integers q - zero_point, cache->k_scale multiplies the softmax
+ * scale (1.442695041f * scale * k_scale, in that association) and cache->v_scale the output.  O
+ * and L are bit for bit what mfa_paged_prefill_forward gives over 16-bit pools holding q - zp at
+ * softmax scale scale * k_scale, with O multiplied by v_scale; for pools mfa_paged_kv_append
+ * wrote they are the attention over the values k_scale * (q - zp), v_scale * (q - zp).
+ * FP16 / BF16 pools (of the query's type) take mfa_paged_prefill_forward's launch and give its
+ * bits, so one function serves whatever the cache holds.  INT4 pools: MFA_ERR_UNSUPPORTED.
+ * INT8 rules (the decode call's): D % 16 == 0, D <= 256; zero points in [-128, 128]; strides in
+ * elements of one byte, multiples of 16 bytes, token stride >= D and below 2^24 bytes; a positive
+ * softmax scale, k_scale > 0 and a positive product of the two.  No host read, no
+ * synchronisation, no workspace other than the scratch L; valid under stream capture. */
+mfa_status_t mfa_quantized_paged_prefill_forward(const mfa_paged_prefill_descriptor_t* desc,
+                                                 const void* query, const int64_t* query_strides,
+                                                 const int32_t* new_lens,
+                                                 const mfa_paged_kv_cache_t* cache,
+                                                 float* output, void* logsumexp, void* stream);
+/* The kernel that call launches (see mfa_multihead_plan).  cache == NULL plans a 16-bit cache of
+ * 256-key pages; NULL pointers inside a cache plan aligned buffers. */
+mfa_status_t mfa_quantized_paged_prefill_plan(const mfa_paged_prefill_descriptor_t* desc,
+                                              const mfa_paged_kv_cache_t* cache,
+                                              mfa_kernel_plan_t* out);
 
 /* ---------------------------------------------------------------------------------- */
 /* Paged MLA decode: absorbed attention over a paged latent cache.  (No reference      */

@@ -2127,12 +2127,16 @@ mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void*
 
 // Paged prefill (attention_prefill_paged.hip): the R rows of each sequence in `query` — a prompt
 // or a chunk of one, ragged through new_lens — attend to the cache they were appended to.  One
-// launch of 128-row query blocks, no workspace but the scratch L; 16-bit pools only.
+// launch of 128-row query blocks, no workspace but the scratch L.  allow_i8 = false
+// (mfa_paged_prefill_forward): 16-bit pools only.  allow_i8 = true
+// (mfa_quantized_paged_prefill_forward): INT8 pools as well, widened on load
+// (attention_prefill_paged_kv8.hip) with the decode call's folded scales; 16-bit pools take the
+// same launch either way.
 mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const void* query,
                            const int64_t* query_strides, const int32_t* new_lens,
                            const mfa_paged_kv_cache_t* cache, float* output, void* logsumexp,
-                           hipStream_t stream) {
-  const char* const what = "paged prefill";
+                           hipStream_t stream, bool allow_i8) {
+  const char* const what = allow_i8 ? "quantized paged prefill" : "paged prefill";
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const mfa_attention_descriptor_t& base = desc->base;
   const int64_t B = desc->batch_size, H = desc->num_heads, Hkv = desc->num_kv_heads;
@@ -2149,14 +2153,16 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
     return fail(MFA_ERR_UNSUPPORTED, "%s: query precision %d (FP16 or BF16)", what, qprec);
   PagedCacheView cv;
   mfa_status_t st =
-      paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", false, &cv);
+      paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", allow_i8, &cv);
   if (st != MFA_SUCCESS) return st;
   if (base.has_sparse_mask || (base.sparsity_pattern != MFA_SPARSITY_NONE &&
                                base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
     return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);
   if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
   const float scale = resolve_scale(base, (int)D);
-  if (!(scale > 0.f) || !(1.442695041f * scale > 0.f))
+  // The decode call's rule and association; 16-bit pools fold 1 (the same bits as without).
+  const float fk = cv.i8 ? cache->k_scale : 1.f, fv = cv.i8 ? cache->v_scale : 1.f;
+  if (!(scale > 0.f) || !(fk > 0.f) || !(1.442695041f * scale * fk > 0.f))
     return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
   if (B * H * R >= ((int64_t)1 << 31))
     return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
@@ -2180,12 +2186,14 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
   if ((st = l_or_scratch(logsumexp, B * H * R, stream, &p.l)) != MFA_SUCCESS) return st;
   p.B = (int)B; p.H = (int)H; p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
   p.C = (int)cv.cap;
-  p.c_log2 = 1.442695041f * scale;
-  p.o_mul = 1.f;
+  p.c_log2 = 1.442695041f * scale * fk;
+  p.o_mul = fv;
   p.mask.causal = base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
   p.mask.skip_ok = 1;
 
-  const hipError_t e = mfa::fwd_prefill_paged_dispatch(p, cv.pg, new_lens, elem, stream);
+  const hipError_t e = cv.i8
+                           ? mfa::fwd_prefill_paged_kv8_dispatch(p, cv.pg, new_lens, elem, stream)
+                           : mfa::fwd_prefill_paged_dispatch(p, cv.pg, new_lens, elem, stream);
   if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
   return hip_status(e, "mfa_fwd (paged prefill) launch");
 }
@@ -2517,7 +2525,7 @@ extern "C" mfa_status_t mfa_paged_prefill_forward(const mfa_paged_prefill_descri
                                                   const mfa_paged_kv_cache_t* cache, float* output,
                                                   void* logsumexp, void* stream) {
   return paged_prefill(desc, query, query_strides, new_lens, cache, output, logsumexp,
-                       (hipStream_t)stream);
+                       (hipStream_t)stream, false);
 }
 
 extern "C" mfa_status_t mfa_paged_prefill_plan(const mfa_paged_prefill_descriptor_t* desc,
@@ -2527,7 +2535,26 @@ extern "C" mfa_status_t mfa_paged_prefill_plan(const mfa_paged_prefill_descripto
   return paged_plan(*desc, resolve_precisions(desc->base).mem[MFA_OPERAND_Q], cache, out,
                     [&](const mfa_paged_kv_cache_t& c) {
                       return paged_prefill(desc, (const void*)kPlanDummy, nullptr, nullptr, &c,
-                                           (float*)kPlanDummy, nullptr, nullptr);
+                                           (float*)kPlanDummy, nullptr, nullptr, false);
+                    });
+}
+
+extern "C" mfa_status_t mfa_quantized_paged_prefill_forward(
+    const mfa_paged_prefill_descriptor_t* desc, const void* query, const int64_t* query_strides,
+    const int32_t* new_lens, const mfa_paged_kv_cache_t* cache, float* output, void* logsumexp,
+    void* stream) {
+  return paged_prefill(desc, query, query_strides, new_lens, cache, output, logsumexp,
+                       (hipStream_t)stream, true);
+}
+
+extern "C" mfa_status_t mfa_quantized_paged_prefill_plan(
+    const mfa_paged_prefill_descriptor_t* desc, const mfa_paged_kv_cache_t* cache,
+    mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return paged_plan(*desc, resolve_precisions(desc->base).mem[MFA_OPERAND_Q], cache, out,
+                    [&](const mfa_paged_kv_cache_t& c) {
+                      return paged_prefill(desc, (const void*)kPlanDummy, nullptr, nullptr, &c,
+                                           (float*)kPlanDummy, nullptr, nullptr, true);
                     });
 }
 

@@ -79,6 +79,10 @@ hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int 
 // rows per sequence in the query, p.C the cap on every length; new_lens: device [B] or NULL.
 hipError_t fwd_prefill_paged_dispatch(const FwdParams& p, const PagedKv& pg,
                                       const int32_t* new_lens, int elem, hipStream_t stream);
+// The same call over per-tensor INT8 pools widened on load (attention_prefill_paged_kv8.hip):
+// p.k.ss in bytes, p.k.zp / p.v.zp the zero points, the scales folded into p.c_log2 and p.o_mul.
+hipError_t fwd_prefill_paged_kv8_dispatch(const FwdParams& p, const PagedKv& pg,
+                                          const int32_t* new_lens, int elem, hipStream_t stream);
 // The write side of that cache (paged_append.hip): one launch scatters the new key and value
 // rows (16-bit, type `elem`) into 16-bit pools of the same type or, with i8, quantises them into
 // per-tensor INT8 pools.  operands = 2: key and value; 1: index 0 of each pair alone (the latent

@@ -593,6 +593,10 @@ _sig("mfa_paged_prefill_forward", ctypes.c_int,
      [_P(PagedPrefillDescriptor), _V, _P(ctypes.c_int64), _V, _P(PagedKVCache), _V, _V, _V])
 _sig("mfa_paged_prefill_plan", ctypes.c_int,
      [_P(PagedPrefillDescriptor), _P(PagedKVCache), _P(KernelPlan)])
+_sig("mfa_quantized_paged_prefill_forward", ctypes.c_int,
+     [_P(PagedPrefillDescriptor), _V, _P(ctypes.c_int64), _V, _P(PagedKVCache), _V, _V, _V])
+_sig("mfa_quantized_paged_prefill_plan", ctypes.c_int,
+     [_P(PagedPrefillDescriptor), _P(PagedKVCache), _P(KernelPlan)])
 _sig("mfa_paged_kv_append", ctypes.c_int,
      [_P(PagedAppendDescriptor), _V, _V, _P(ctypes.c_int64), _P(ctypes.c_int64), _V,
       _P(PagedKVCache), _V])
@@ -882,6 +886,25 @@ def paged_prefill_plan(desc: PagedPrefillDescriptor,
     """mfa_paged_prefill_plan: the kernel paged_prefill_forward launches (see multihead_plan);
     without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
     return _paged_plan(lib.mfa_paged_prefill_plan, desc, cache)
+
+
+def quantized_paged_prefill_forward(desc: PagedPrefillDescriptor, query, cache: PagedKVCache,
+                                    output, new_lens=None, logsumexp=None, query_strides=None,
+                                    stream=None):
+    """mfa_quantized_paged_prefill_forward: paged_prefill_forward over a cache whose pools may be
+    per-tensor INT8 (widened on load; cache.k_scale multiplies the softmax scale, cache.v_scale
+    the output, as in paged_decode_forward).  16-bit pools run paged_prefill_forward's kernel."""
+    s = _strides(query_strides)
+    check(lib.mfa_quantized_paged_prefill_forward(
+        ctypes.byref(desc), _ptr(query), s[0] if s else None, _ptr(new_lens), ctypes.byref(cache),
+        _ptr(output), _ptr(logsumexp), _stream(stream)))
+
+
+def quantized_paged_prefill_plan(desc: PagedPrefillDescriptor,
+                                 cache: Optional[PagedKVCache] = None) -> list[dict]:
+    """mfa_quantized_paged_prefill_plan: the kernel quantized_paged_prefill_forward launches (see
+    multihead_plan); without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
+    return _paged_plan(lib.mfa_quantized_paged_prefill_plan, desc, cache)
 
 
 def paged_kv_append(desc: PagedAppendDescriptor, key, value, cache: PagedKVCache, new_lens=None,
