@@ -101,12 +101,17 @@ typedef enum mfa_operand {
 int mfa_operand_buffer_binding(mfa_operand_t operand);
 
 /* SparsityPattern (AttentionDescriptor.swift:10-15). `custom` is accepted and treated as
- * none, exactly as AttentionDescriptor.setFunctionConstants does (:226-229). */
+ * none, exactly as AttentionDescriptor.setFunctionConstants does (:226-229).
+ * MFA_SPARSITY_CAUSAL_WINDOW has no Swift counterpart (the reference's slidingWindow is
+ * one-sided, row > col + window, and not causal): it is the causal sliding window of a KV
+ * cache, window_size = W, served by the paged K/V calls alone (see "Causal window" in the
+ * paged section below); every other call returns MFA_ERR_UNSUPPORTED for it. */
 typedef enum mfa_sparsity {
   MFA_SPARSITY_NONE = 0,
   MFA_SPARSITY_CAUSAL = 1,
   MFA_SPARSITY_SLIDING_WINDOW = 2,
   MFA_SPARSITY_CUSTOM = 3,
+  MFA_SPARSITY_CAUSAL_WINDOW = 4,
   MFA_SPARSITY_RANGE_MIN_ = -0x7fffffff - 1, /* range sentinel (see mfa_status) */
   MFA_SPARSITY_RANGE_MAX_ = 0x7fffffff
 } mfa_sparsity_t;
@@ -133,7 +138,7 @@ typedef struct mfa_attention_descriptor {
   int32_t has_transpose_state;           /* Optional transposeState */
   int32_t transpose_q, transpose_k, transpose_v, transpose_o;
   int32_t sparsity_pattern;              /* mfa_sparsity_t */
-  uint32_t window_size;                  /* slidingWindow(windowSize:) */
+  uint32_t window_size;                  /* slidingWindow(windowSize:); W of CAUSAL_WINDOW */
   int32_t has_softmax_scale;             /* Optional softmaxScale; default 1/sqrt(D) */
   float softmax_scale;
   int32_t has_sparse_mask;               /* Optional sparseMask */
@@ -509,8 +514,29 @@ typedef struct mfa_paged_kv_cache {
   uint32_t num_pages;            /* pages in the pools */
 } mfa_paged_kv_cache_t;
 
+/* Causal window (MFA_SPARSITY_CAUSAL_WINDOW, window_size = W; no reference counterpart): the
+ * local-attention mask of a KV cache, served by mfa_paged_decode_forward (16-bit and INT8 pools,
+ * both row forms), mfa_paged_prefill_forward, mfa_quantized_paged_prefill_forward and their three
+ * *_plan functions.  Row q sits at key position t_q exactly as under MFA_SPARSITY_CAUSAL (decode:
+ * len_b - R + q; prefill: len_b - n_b + q) and attends to keys j with t_q - W <= j <= t_q: W + 1
+ * keys, the reference's row > col + window rule joined with the KV-cache causal rule.  W >= 2^30
+ * is treated as 2^30, which is plain causal (bit for bit the MFA_SPARSITY_CAUSAL result); W = 0
+ * leaves each row its own key.  Dead rows (q >= n_b, t_q < 0, len_b == 0) keep their result:
+ * exact zeros, L at its floor, never NaN; a live row always sees key t_q.
+ * Page release.  Let t_first be the position of the sequence's first live row (decode:
+ * max(0, len_b - R); prefill: max(0, len_b - n_b)) and lo_b = max(0, t_first - W).  No byte of a
+ * logical page that lies wholly below lo_b (its last key < lo_b) is fetched, the block-table entry
+ * of such a page may hold any value, and the result depends on neither: a serving loop may hand
+ * those pages back to its allocator.  Everything else in the calls' safety rules stays: clamped
+ * page ids, clamped table index, no read at or past len_b.
+ * The decode call sizes its split layout, grid and workspace from
+ * min(min(max_seq_len, max_pages_per_seq * page_size), W + R + 31) keys instead of the cap, so a
+ * step costs the window, not the cache.
+ * MFA_SPARSITY_SLIDING_WINDOW stays MFA_ERR_UNSUPPORTED on every paged call; the paged MLA calls,
+ * mfa_multihead_forward / backward, mfa_quantized_forward* and mfa_mla_forward* return
+ * MFA_ERR_UNSUPPORTED for MFA_SPARSITY_CAUSAL_WINDOW. */
 typedef struct mfa_paged_decode_descriptor {
-  mfa_attention_descriptor_t base;   /* precision of Q, scale, sparsity (NONE or CAUSAL), L precision */
+  mfa_attention_descriptor_t base;   /* precision of Q, scale, sparsity (NONE, CAUSAL or CAUSAL_WINDOW), L precision */
   uint32_t batch_size, num_heads, num_kv_heads;
   uint32_t rows;                     /* R: query rows per head */
   uint32_t head_dim;
@@ -525,14 +551,16 @@ typedef struct mfa_paged_decode_descriptor {
  * MFA_SPARSITY_CAUSAL — row q attends to keys j <= seq_lens[b] - R + q: the KV-cache
  * convention (the R new tokens are already appended and the last row sees every key), which
  * differs from the top-left diagonal of mfa_multihead_forward (key <= query index) and needs
- * seq_lens[b] >= R.  Sliding windows and sparse masks: MFA_ERR_UNSUPPORTED.
+ * seq_lens[b] >= R.  MFA_SPARSITY_CAUSAL_WINDOW — the causal mask cut to keys j >= t_q - W
+ * ("Causal window" above, with its page-release contract).  MFA_SPARSITY_SLIDING_WINDOW and
+ * sparse masks: MFA_ERR_UNSUPPORTED.
  * A sequence of length 0 gets output rows of exact zeros (for INT8 pools with v_scale < 4) and
  * L = -FLT_MAX in FP32, -inf in FP16: finite or -inf, never NaN.
  * Supported: D % 8 == 0 (INT8: D % 16 == 0), D <= 256; 16-byte aligned pools, query and strides
  * (in bytes), token stride below 2^24 bytes; B * H_kv * ceil((H / H_kv) * R / 32) < 65536; a
  * positive softmax scale (and k_scale); min(max_seq_len, max_pages_per_seq * page_size) <= 2^30.
  * batch_size == 0 or rows == 0 succeeds and launches nothing.  The split-KV partials live in
- * library scratch (mfa_release_scratch), sized by max_seq_len. */
+ * library scratch (mfa_release_scratch), sized by max_seq_len (causal window: by the window). */
 mfa_status_t mfa_paged_decode_forward(const mfa_paged_decode_descriptor_t* desc,
                                       const void* query, const int64_t* query_strides,
                                       const mfa_paged_kv_cache_t* cache,
@@ -590,7 +618,7 @@ mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descriptor_t* desc,
                                       const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
 
 typedef struct mfa_paged_prefill_descriptor {
-  mfa_attention_descriptor_t base;   /* precision of Q, scale, sparsity (NONE or CAUSAL), L precision */
+  mfa_attention_descriptor_t base;   /* precision of Q, scale, sparsity (NONE, CAUSAL or CAUSAL_WINDOW), L precision */
   uint32_t batch_size, num_heads, num_kv_heads;
   uint32_t rows;                     /* R: query rows per sequence in `query` (upper bound when new_lens is given) */
   uint32_t head_dim;
@@ -611,8 +639,9 @@ typedef struct mfa_paged_prefill_descriptor {
  * key position t_q = len_b - n_b + q, the slot mfa_paged_kv_append wrote its key to.
  * Masks: MFA_SPARSITY_CAUSAL — row q attends to keys j <= t_q: the decode call's KV-cache
  * convention, per sequence and ragged; with n_b == len_b it is a plain causal prompt prefill.
- * MFA_SPARSITY_NONE — row q attends to keys 0 .. len_b - 1.  Sliding windows and sparse masks:
- * MFA_ERR_UNSUPPORTED.
+ * MFA_SPARSITY_NONE — row q attends to keys 0 .. len_b - 1.  MFA_SPARSITY_CAUSAL_WINDOW — keys
+ * t_q - W <= j <= t_q ("Causal window" above, with its page-release contract).
+ * MFA_SPARSITY_SLIDING_WINDOW and sparse masks: MFA_ERR_UNSUPPORTED.
  * Rows that are not a position of their sequence — q >= n_b; t_q < 0 because n_b > len_b; any row
  * when len_b == 0 — have no visible key under either mask and get output rows of exact zeros and
  * L = -FLT_MAX in FP32, -inf in FP16 (the decode call's empty-sequence result), never NaN.  So
@@ -714,7 +743,7 @@ typedef struct mfa_paged_mla_descriptor {
  * Masks: MFA_SPARSITY_NONE — every row attends to keys 0 .. len_b - 1; MFA_SPARSITY_CAUSAL —
  * row q attends to keys j <= len_b - R + q: mfa_paged_decode_forward's KV-cache convention (the
  * R new tokens are already appended), not the top-left diagonal of mfa_mla_forward_absorbed.
- * Sliding windows and sparse masks: MFA_ERR_UNSUPPORTED.
+ * Sliding windows (MFA_SPARSITY_CAUSAL_WINDOW included) and sparse masks: MFA_ERR_UNSUPPORTED.
  * Rows with no visible key — every row when len_b == 0, causal rows with len_b - R + q < 0 — get
  * output rows of exact zeros and L = -FLT_MAX in FP32, -inf in FP16 (the paged calls' empty-row
  * result), never NaN; every row of output and logsumexp is written, for any device values.
@@ -756,7 +785,8 @@ mfa_status_t mfa_paged_mla_decode_plan(const mfa_paged_mla_descriptor_t* desc,
  * (new_lens: device [B], nullable, never read by the host).  Row q < n_b of sequence b is key
  * position t_q = len_b - n_b + q — the slot mfa_paged_latent_append wrote with the same cache,
  * new_lens and rows.  MFA_SPARSITY_CAUSAL: row q attends to keys j <= t_q; MFA_SPARSITY_NONE:
- * to keys 0 .. len_b - 1.  Sliding windows and sparse masks: MFA_ERR_UNSUPPORTED.
+ * to keys 0 .. len_b - 1.  Sliding windows (MFA_SPARSITY_CAUSAL_WINDOW included) and sparse
+ * masks: MFA_ERR_UNSUPPORTED.
  * Dead rows — q >= n_b, t_q < 0, every row when len_b == 0 — get output rows of exact zeros and
  * L = -FLT_MAX in FP32, -inf in FP16; every row of output and logsumexp is written, for any
  * device values, never with NaN.  The contents of query rows q >= n_b are never used: they may

@@ -292,6 +292,7 @@ __device__ __forceinline__ void decode_finish16(const DecodeParams& dp, char* sm
 // scalar load issued two tiles before the tile's own K/V loads) and in the causal diagonal,
 // which ends at the sequence's last key.  Split layout, partials and merge are the same; a
 // split past a sequence's end has no tiles and writes the neutral partial (-FLT_MAX, 0, 0).
+// Under the causal window the paged splits start at the window's base (kv_split_start), not at key 0.
 struct ContiguousKv {
   static constexpr bool paged = false;
 };
@@ -309,6 +310,30 @@ __device__ __forceinline__ int kv_len(const FwdParams& p, const PG& pg, int b) {
     return min(max(((const_i32_ptr)pg.seq_lens)[b], 0), p.C);
   else
     return p.C;
+}
+
+// First key of split `split` of a sequence of len keys: split · chunk from the layout's base.
+// The base is 0 for every contiguous cache and for paged calls without a window.  Paged, under
+// the causal window: no row sees a key below len - R - W, so the layout starts at the 32-key tile
+// that key lies in and the pages wholly below it are never addressed (mfa.h, "Causal window": the
+// page-release contract); the host sizes the layout from W + R + 31 keys (decode_paged_span).
+// The result is wave-uniform and stays on the scalar path with len.  It is handed on as one
+// opaque scalar: left visible, the sum is reassociated into the per-lane mask offsets
+// (qcol - base - split · chunk, two vector subtractions per offset), which takes the INT8 16-row
+// D = 256 kernel past its 256 registers.
+template <class PG>
+__device__ __forceinline__ int kv_split_start(const FwdParams& p, int len, int split, int chunk) {
+  if constexpr (PG::paged) {
+    const int base =
+        p.mask.window
+            ? max(max(len - p.R, 0) - (int)min(p.mask.window_size, 0x40000000u), 0) & ~31
+            : 0;
+    int k0 = base + split * chunk;
+    __asm__ __volatile__("" : "+s"(k0));
+    return k0;
+  } else {
+    return split * chunk;
+  }
 }
 
 // Block-table entry for key t (wave-uniform) of batch item b, as stored: kv_tile clamps it to
@@ -435,7 +460,7 @@ __device__ __forceinline__ void decode16_kv16(const DecodeParams& dp, const PG& 
   }
 
   // Keys of this split: [k0, k1); this wave's tiles k0 + BK·(wave + 4i).
-  const int k0 = split * dp.chunk;
+  const int k0 = kv_split_start<PG>(p, C, split, dp.chunk);
   const int k1 = min(C, k0 + dp.chunk);
   const int nt = k1 > k0 ? (k1 - k0 + BK - 1) / BK : 0;
   // Paged bodies keep the tile bookkeeping on the scalar path (the wave id is uniform).
@@ -615,7 +640,7 @@ __device__ __forceinline__ void decode32_kv16(const DecodeParams& dp, const PG& 
     }
   }
 
-  const int k0 = split * dp.chunk;
+  const int k0 = kv_split_start<PG>(p, C, split, dp.chunk);
   const int k1 = min(C, k0 + dp.chunk);
   const int nt = k1 > k0 ? (k1 - k0 + BK - 1) / BK : 0;
   // Paged bodies keep the tile bookkeeping on the scalar path (the wave id is uniform).
@@ -1196,13 +1221,16 @@ static hipError_t launch_merge(hipError_t e, const DecodeParams& dp, hipStream_t
 }
 
 // What both dispatchers derive from a call over C keys (p.C is ignored): in *dp the split layout
-// and the partials workspace carved up; returned, the grid and the padded head dimension.
+// over `span` keys and the partials workspace carved up; returned, the grid and the padded head
+// dimension.  span == C but for the paged causal window, whose splits cover the window's keys
+// from the window's base on while C stays the cap that kv_len clamps against.
 struct DecodeLaunch { hipError_t err; dim3 grid; int DP; };
-static DecodeLaunch decode_params(const FwdParams& p, int C, void* workspace, DecodeParams* dp) {
+static DecodeLaunch decode_params(const FwdParams& p, int C, int span, void* workspace,
+                                  DecodeParams* dp) {
   dp->f = p;
   dp->f.C = C;
   dp->rows = (p.H / p.Hkv) * p.R;
-  decode_layout(p.B, p.Hkv, dp->rows, C, &dp->nrt, &dp->nsplit, &dp->chunk);
+  decode_layout(p.B, p.Hkv, dp->rows, span, &dp->nrt, &dp->nsplit, &dp->chunk);
   const size_t parts = (size_t)p.B * p.Hkv * dp->nrt * dp->nsplit * 32;
   dp->opart = (float*)workspace;
   dp->mlpart = workspace ? (float2*)((char*)workspace + ((parts * p.D * 4 + 255) & ~(size_t)255))
@@ -1222,7 +1250,8 @@ hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hi
     return hipErrorNotSupported;
   DecodeParams dp;
   // Causal (key <= query index): no row sees a key past R - 1.
-  const DecodeLaunch dl = decode_params(p, decode_keys(p.R, p.C, p.mask.causal), workspace, &dp);
+  const int keys = decode_keys(p.R, p.C, p.mask.causal);
+  const DecodeLaunch dl = decode_params(p, keys, keys, workspace, &dp);
   if (dl.err != hipSuccess) return dl.err;
   const dim3 grid = dl.grid;
   const int DP = dl.DP;
@@ -1267,9 +1296,18 @@ hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hi
   return launch_merge(e, dp, stream);
 }
 
+// Keys the split layout of a paged call covers: the cap, or under the causal window the R + W
+// keys any row sees plus the 32-key alignment of the base (64-bit: W reaches 2^30).  With
+// W + R + 31 >= cap it is the cap, the base is 0 and the layout is the causal call's.
+int decode_paged_span(int cap, int R, bool window, uint32_t window_size) {
+  if (!window) return cap;
+  const int64_t span = (int64_t)window_size + R + 31;
+  return span < cap ? (int)span : cap;
+}
+
 // The paged forms.  p.C is the host-side cap on every sequence's length: split layout, grid and
-// workspace follow it (the lengths are device values), p.k / p.v are the pools (16-bit in the
-// compute type, or per-tensor INT8).
+// workspace follow decode_paged_span of it (the lengths are device values), p.k / p.v are the
+// pools (16-bit in the compute type, or per-tensor INT8).
 hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int elem,
                                      void* workspace, hipStream_t stream) {
   const bool kv16 = p.k.prec == elem && (elem == P_FP16 || elem == P_BF16);
@@ -1277,7 +1315,8 @@ hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int 
     return hipErrorNotSupported;
   PagedDecodeParams pp;
   pp.pg = pg;
-  const DecodeLaunch dl = decode_params(p, p.C, workspace, &pp.d);
+  const DecodeLaunch dl = decode_params(
+      p, p.C, decode_paged_span(p.C, p.R, p.mask.window, p.mask.window_size), workspace, &pp.d);
   if (dl.err != hipSuccess) return dl.err;
   const dim3 grid = dl.grid;
   const int DP = dl.DP;

@@ -30,7 +30,9 @@
 //     pools where it is used; all tile bookkeeping is wave-uniform.
 // Causal: the key loop ends at the block's last visible key, and the grid runs the heaviest
 // (last) row blocks of every (b, h) first; the lengths are device values, so a block past n_b
-// costs one early exit.
+// costs one early exit.  Causal window (MFA_SPARSITY_CAUSAL_WINDOW): mfa_paged_window_prefill_kernel,
+// the same body with WIN set (prefill_paged_body.h), whose key loop also starts at the block's
+// first visible tile and which never fetches a segment wholly below the window.
 //
 // Not here (DESIGN.md §3 "Paged prefill"): K/V tiles shared between the query heads of a kv
 // group, split-KV for a short chunk over a very long prefix (the decode call's shape).  INT8
@@ -91,108 +93,15 @@ struct PagedDma {
 
 template <class E, int DP, int BK>
 __global__ void __launch_bounds__(256, 2) mfa_paged_prefill_kernel(PagedPrefillParams pp) {
-  constexpr int NT = 256, BQ = 128;
-  constexpr int TILEB = BK * DP * 2;
-  using Dma = PagedDma<DP, BK, NT>;
-  constexpr int NSEG = Dma::NSEG;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const kb0 = smem;
-  char* const vb0 = smem + 2 * TILEB;
-  const FwdParams& p = pp.f;
-  const PagedKv& pg = pp.pg;
+  constexpr bool WIN = false;
+#include "prefill_paged_body.h"
+}
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int l32 = lane & 31, hh = lane >> 5;
-  const int rbase[2] = {TileA<DP>::row_base(l32, hh, 0), TileA<DP>::row_base(l32, hh, 1)};
-  const int trb[2] = {TileA<DP>::tr_base(lane, 0), TileA<DP>::tr_base(lane, 1)};
-  // Causal: heaviest blocks first over the whole grid (balance); otherwise each head's blocks
-  // together on one XCD (L2 reuse of its K/V).
-  int bh, blk;
-  if (p.mask.causal) {
-    bh = blockIdx.x % (p.B * p.H);
-    blk = blockIdx.x / (p.B * p.H);
-  } else {
-    xcd_unit_block(blockIdx.x, p.B * p.H, p.nblk, &bh, &blk);
-  }
-  const int rb = p.nblk - 1 - blk;
-  const int b = bh / p.H, h = bh % p.H, kvh = h % p.Hkv;
-  const int q0 = rb * BQ;
-  const int q = q0 + wave * 32 + l32;
-
-  // The sequence's keys and rows (uniform).  p.C is the host-side cap on every length.
-  const int len = min(max(((prefill_i32_ptr)pg.seq_lens)[b], 0), p.C);
-  const int n = pp.new_lens ? min(max(((prefill_i32_ptr)pp.new_lens)[b], 0), p.R) : p.R;
-  const int shift = len - n;              // row q is key position shift + q
-  // Keys of this block: up to its last live row's position (causal), or all of them.
-  const int qlast = min(q0 + BQ, n) - 1;  // last row of the block that belongs to the sequence
-  const int kend = p.mask.causal ? min(len, shift + qlast + 1) : len;
-  if (q0 >= n || kend <= 0) {
-    // No live row: nothing of the cache is read.
-    if (q < p.R) store_dead_row<DP>(p, b, h, q, hh);
-    return;
-  }
-  const int tq = shift + q;
-  const bool live = q < n && tq >= 0;
-  // The body's view: len keys, the lane's query at key position tq (dead rows: masked wherever
-  // the causal mask is applied; their result is replaced below).
-  FwdParams lp = p;
-  lp.C = len;
-  const int qpos = live ? tq : -1;
-  const float c = p.c_log2;
-
-  const int ssb = (int)p.k.ss * 2, dbytes = 2 * p.D;
-  const char* khead = (const char*)p.k.ptr + (int64_t)kvh * pg.head_bytes;
-  const char* vhead = (const char*)p.v.ptr + (int64_t)kvh * pg.head_bytes;
-  Dma dma;  // K and V share the pool layout: one set of lane offsets
-  dma.init(ssb, dbytes, tid);
-  // Tile at key t with its segments' block-table entries `pages` into ring slot `slot`.
-  auto stage = [&](int t, const int (&pages)[NSEG], int slot) {
-    int64_t rel[NSEG];
-    int nb[NSEG];
-#pragma unroll
-    for (int s = 0; s < NSEG; ++s)
-      rel[s] = prefill_segment(pg, pages[s], t + 32 * s, len, ssb, dbytes, &nb[s]);
-    dma.issue(khead, rel, nb, kb0 + slot * TILEB);
-    dma.issue(vhead, rel, nb, vb0 + slot * TILEB);
-  };
-  int pgn[NSEG];  // entries of the next tile to stage
-#pragma unroll
-  for (int s = 0; s < NSEG; ++s) pgn[s] = prefill_page(pg, b, 32 * s);
-  stage(0, pgn, 0);
-#pragma unroll
-  for (int s = 0; s < NSEG; ++s) pgn[s] = prefill_page(pg, b, BK + 32 * s);
-
-  i16x8 qf[DP / 16];
-  load_q2<E, DP>(qf, p, b, h, q, live, hh, c);
-  RowState<DP> st;
-  st.init();
-  wait_vm();
-  __syncthreads();
-
-  int cur = 0;
-  for (int t = 0; t < kend; t += BK) {
-    if (t + BK < kend) {
-      stage(t + BK, pgn, cur ^ 1);
-      // The entries of the tile after it: a whole tile's compute before they are used.
-#pragma unroll
-      for (int s = 0; s < NSEG; ++s) pgn[s] = prefill_page(pg, b, t + 2 * BK + 32 * s);
-    }
-    // The block's first row bounds the tiles every live row sees whole.
-    const bool mask_tile = (t + BK > len) || (p.mask.causal && t + BK - 1 > shift + q0);
-    fwd2_tile<E, DP, BK>(kb0 + cur * TILEB, vb0 + cur * TILEB, rbase, trb, qf, st, t, mask_tile,
-                         qpos, lp, c, 0x3fffffff, hh);
-    wait_vm();
-    __syncthreads();
-    cur ^= 1;
-  }
-
-  float l = cross_half_sum(st.lh) + kFltMin;
-  if (!(l > 0.f)) l = kFltMin;
-  if (live)
-    store_o_l<DP>(p, st.o, st.m, l, b, h, q, hh);
-  else if (q < p.R)
-    store_dead_row<DP>(p, b, h, q, hh);
+// The same under the causal window.
+template <class E, int DP, int BK>
+__global__ void __launch_bounds__(256, 2) mfa_paged_window_prefill_kernel(PagedPrefillParams pp) {
+  constexpr bool WIN = true;
+#include "prefill_paged_body.h"
 }
 
 // One launch; grid = (batch · heads · 128-row blocks).  p.C is the cap on every length, p.k / p.v
@@ -211,8 +120,11 @@ hipError_t fwd_prefill_paged_dispatch(const FwdParams& p, const PagedKv& pg,
   const int DP = p.D <= 64 ? 64 : p.D <= 128 ? 128 : 256;
 #define MFA_PREFILL(ELEM, EE, DPV, BKV)                                                       \
   if (elem == ELEM && DP == DPV)                                                              \
-    return launch(mfa_paged_prefill_kernel<EE, DPV, BKV>, grid, block, 4 * BKV * DPV * 2,     \
-                  stream, pp);
+    return p.mask.window                                                                      \
+               ? launch(mfa_paged_window_prefill_kernel<EE, DPV, BKV>, grid, block,           \
+                        4 * BKV * DPV * 2, stream, pp)                                        \
+               : launch(mfa_paged_prefill_kernel<EE, DPV, BKV>, grid, block,                  \
+                        4 * BKV * DPV * 2, stream, pp);
   MFA_PREFILL(P_FP16, F16, 64, 64)
   MFA_PREFILL(P_FP16, F16, 128, 64)
   MFA_PREFILL(P_FP16, F16, 256, 32)

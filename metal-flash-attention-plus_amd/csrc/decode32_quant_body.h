@@ -73,7 +73,7 @@
   }
 
   // Keys of this split: [k0, k1); this wave's tiles k0 + 32·(wave + 4i).
-  const int k0 = split * dp.chunk;
+  const int k0 = kv_split_start<PG>(p, C, split, dp.chunk);
   const int k1 = min(C, k0 + dp.chunk);
   const int nt = k1 > k0 ? (k1 - k0 + BK - 1) / BK : 0;
   // Paged bodies keep the tile bookkeeping on the scalar path (the wave id is uniform).

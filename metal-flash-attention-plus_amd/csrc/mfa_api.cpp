@@ -224,6 +224,13 @@ struct MaskPlan {
   mfa::MaskArgs args;
 };
 
+// MFA_SPARSITY_CAUSAL_WINDOW is a known value that only the paged K/V calls serve.
+mfa_status_t causal_window_unserved(const char* what) {
+  return fail(MFA_ERR_UNSUPPORTED,
+              "%s: MFA_SPARSITY_CAUSAL_WINDOW (%d) is served by the paged K/V decode and prefill "
+              "calls only", what, (int)MFA_SPARSITY_CAUSAL_WINDOW);
+}
+
 mfa_status_t plan_masks(const mfa_attention_descriptor_t& base, const void* mask, int R, int C,
                         mfa::MaskArgs* out) {
   memset(out, 0, sizeof(*out));
@@ -236,6 +243,7 @@ mfa_status_t plan_masks(const mfa_attention_descriptor_t& base, const void* mask
       out->window = 1;
       out->window_size = base.window_size;
       break;
+    case MFA_SPARSITY_CAUSAL_WINDOW: return causal_window_unserved("this call");
     default: return fail(MFA_ERR_INVALID_DESCRIPTOR, "unknown sparsity pattern %d",
                          base.sparsity_pattern);
   }
@@ -650,6 +658,8 @@ mfa_status_t plan_multihead(const mfa_multihead_descriptor_t* desc, const void* 
                 desc->broadcast_mode);
   const mfa_attention_descriptor_t& base = desc->base;
   if (!base.has_transpose_state) return fail(MFA_ERR_INVALID_DESCRIPTOR, "Descriptor was incomplete.");
+  if (base.sparsity_pattern == MFA_SPARSITY_CAUSAL_WINDOW)
+    return causal_window_unserved("multi-head attention");
   pl->B = (int)desc->query_shape.batch_size;
   pl->H = (int)desc->query_shape.num_heads;
   pl->Hkv = (int)desc->key_shape.num_heads;
@@ -882,6 +892,8 @@ extern "C" mfa_status_t mfa_quantized_forward(const mfa_quantized_descriptor_t* 
   if (!desc) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   const mfa_attention_descriptor_t& base = desc->base;
   if (!base.has_matrix_dimensions) return fail(MFA_ERR_INVALID_DESCRIPTOR, "Descriptor was incomplete.");
+  if (base.sparsity_pattern == MFA_SPARSITY_CAUSAL_WINDOW)
+    return causal_window_unserved("quantized attention");
   const int B = desc->batch_size ? (int)desc->batch_size : 1;
   const int H = desc->num_heads ? (int)desc->num_heads : 1;
   const int Hkv = desc->num_kv_heads ? (int)desc->num_kv_heads : H;
@@ -998,6 +1010,8 @@ extern "C" mfa_status_t mfa_quantized_forward_from_float(
   if (!desc) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
   const mfa_attention_descriptor_t& base = desc->base;
   if (!base.has_matrix_dimensions) return fail(MFA_ERR_INVALID_DESCRIPTOR, "Descriptor was incomplete.");
+  if (base.sparsity_pattern == MFA_SPARSITY_CAUSAL_WINDOW)
+    return causal_window_unserved("quantized attention");
   const int precs[3] = {query_precision, key_precision, value_precision};
   for (int p : precs)
     if (p != MFA_PRECISION_FP32 && p != MFA_PRECISION_FP16 && p != MFA_PRECISION_BF16)
@@ -1332,6 +1346,8 @@ mfa_status_t quantized_backward(const mfa_quantized_descriptor_t* desc,
     return fail(MFA_ERR_INVALID_ARGUMENT, "backwardKeyValue requires gradKey and gradValue");
   const mfa_attention_descriptor_t& base = desc->base;
   if (!base.has_matrix_dimensions) return fail(MFA_ERR_INVALID_DESCRIPTOR, "Descriptor was incomplete.");
+  if (base.sparsity_pattern == MFA_SPARSITY_CAUSAL_WINDOW)
+    return causal_window_unserved("quantized attention");
   const int B = desc->batch_size ? (int)desc->batch_size : 1;
   const int H = desc->num_heads ? (int)desc->num_heads : 1;
   const int Hkv = desc->num_kv_heads ? (int)desc->num_kv_heads : H;
@@ -1595,6 +1611,8 @@ extern "C" mfa_status_t mfa_mla_forward(const mfa_mla_descriptor_t* desc, const 
   const int prec = desc->precision;
   if (prec != MFA_PRECISION_FP16 && prec != MFA_PRECISION_BF16)
     return fail(MFA_ERR_UNSUPPORTED, "MLA precision must be FP16 or BF16");
+  if (desc->base.sparsity_pattern == MFA_SPARSITY_CAUSAL_WINDOW)
+    return causal_window_unserved("MLA forward");
   const int B = (int)desc->batch_size, H = (int)desc->num_heads;
   const int Sq = (int)desc->sequence_length_q, Skv = (int)desc->sequence_length_kv;
   const int D = (int)desc->head_dim, Lat = (int)desc->kv_latent_dim;
@@ -1761,6 +1779,7 @@ extern "C" mfa_status_t mfa_mla_forward_absorbed(const mfa_mla_descriptor_t* des
   if (Lat != 256 && Lat != 512)
     return fail(MFA_ERR_UNSUPPORTED, "absorbed MLA needs a latent dimension of 256 or 512 (got %d)", Lat);
   const int sp = desc->base.sparsity_pattern;
+  if (sp == MFA_SPARSITY_CAUSAL_WINDOW) return causal_window_unserved("absorbed MLA forward");
   if (sp != MFA_SPARSITY_NONE && sp != MFA_SPARSITY_CAUSAL)
     return fail(MFA_ERR_UNSUPPORTED, "absorbed MLA supports no mask or causal");
   mfa_status_t st0 = check_transposes(desc->base, false, "absorbed MLA forward");
@@ -1993,8 +2012,25 @@ mfa_status_t paged_plan(const Desc& d, int prec16, const mfa_paged_kv_cache_t* c
   return st;
 }
 
+// The masks of the paged K/V decode and prefill calls: none, causal, and the causal window
+// (MFA_SPARSITY_CAUSAL_WINDOW: keys t_q - W <= j <= t_q; W >= 2^30 is 2^30, plain causal).  A
+// live row always sees its own key, so fully masked tiles may be skipped.
+bool paged_kv_mask_served(const mfa_attention_descriptor_t& base) {
+  return !base.has_sparse_mask && (base.sparsity_pattern == MFA_SPARSITY_NONE ||
+                                   base.sparsity_pattern == MFA_SPARSITY_CAUSAL ||
+                                   base.sparsity_pattern == MFA_SPARSITY_CAUSAL_WINDOW);
+}
+void paged_kv_mask(const mfa_attention_descriptor_t& base, mfa::MaskArgs* m) {
+  const bool win = base.sparsity_pattern == MFA_SPARSITY_CAUSAL_WINDOW;
+  m->causal = win || base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
+  m->window = win;
+  m->window_size = win ? std::min<uint32_t>(base.window_size, 1u << 30) : 0;
+  m->skip_ok = 1;
+}
+
 // Split-KV decode over the cache (attention_decode.hip, the *_paged_kernel entry points).  The
-// split layout, the grid and the partials workspace (library scratch slot 15) follow max_seq_len.
+// split layout, the grid and the partials workspace (library scratch slot 15) follow max_seq_len,
+// or under the causal window the window (decode_paged_span).
 mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void* query,
                           const int64_t* query_strides, const mfa_paged_kv_cache_t* cache,
                           float* output, void* logsumexp, hipStream_t stream) {
@@ -2017,9 +2053,8 @@ mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void*
   mfa_status_t st =
       paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", true, &cv);
   if (st != MFA_SUCCESS) return st;
-  if (base.has_sparse_mask || (base.sparsity_pattern != MFA_SPARSITY_NONE &&
-                               base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);
+  if (!paged_kv_mask_served(base))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal and the causal window", what);
   if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
   const float scale = resolve_scale(base, (int)D);
   const float fk = cv.i8 ? cache->k_scale : 1.f, fv = cv.i8 ? cache->v_scale : 1.f;
@@ -2051,11 +2086,11 @@ mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void*
   p.C = (int)cv.cap;
   p.c_log2 = 1.442695041f * scale * fk;
   p.o_mul = fv;
-  p.mask.causal = base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
-  p.mask.skip_ok = 1;
+  paged_kv_mask(base, &p.mask);
 
   void* ws = nullptr;
-  const size_t wsb = mfa::decode_workspace_bytes((int)B, (int)Hkv, (int)rows, (int)cv.cap, (int)D);
+  const int span = mfa::decode_paged_span((int)cv.cap, (int)R, p.mask.window, p.mask.window_size);
+  const size_t wsb = mfa::decode_workspace_bytes((int)B, (int)Hkv, (int)rows, span, (int)D);
   if (wsb && mfa::plan_capture()) ws = (void*)kPlanDummy;
   else if (wsb && (st = scratch(wsb, &ws, 15, stream)) != MFA_SUCCESS) return st;
   const hipError_t e = mfa::fwd_decode_paged_dispatch(p, cv.pg, elem, ws, stream);
@@ -2155,9 +2190,8 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
   mfa_status_t st =
       paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", allow_i8, &cv);
   if (st != MFA_SUCCESS) return st;
-  if (base.has_sparse_mask || (base.sparsity_pattern != MFA_SPARSITY_NONE &&
-                               base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);
+  if (!paged_kv_mask_served(base))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal and the causal window", what);
   if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
   const float scale = resolve_scale(base, (int)D);
   // The decode call's rule and association; 16-bit pools fold 1 (the same bits as without).
@@ -2188,8 +2222,7 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
   p.C = (int)cv.cap;
   p.c_log2 = 1.442695041f * scale * fk;
   p.o_mul = fv;
-  p.mask.causal = base.sparsity_pattern == MFA_SPARSITY_CAUSAL;
-  p.mask.skip_ok = 1;
+  paged_kv_mask(base, &p.mask);
 
   const hipError_t e = cv.i8
                            ? mfa::fwd_prefill_paged_kv8_dispatch(p, cv.pg, new_lens, elem, stream)
@@ -2284,6 +2317,7 @@ mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* 
   if (D % 8 != 0 || D > 256)
     return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of 8, at most 256)",
                 what, (long long)D);
+  if (base.sparsity_pattern == MFA_SPARSITY_CAUSAL_WINDOW) return causal_window_unserved(what);
   if (base.has_sparse_mask || (base.sparsity_pattern != MFA_SPARSITY_NONE &&
                                base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
     return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);

@@ -70,8 +70,11 @@ size_t decode_workspace_bytes(int B, int Hkv, int rows, int C, int D);
 int decode_keys(int R, int C, bool causal);
 hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hipStream_t stream);
 // The same kernels over a paged, ragged cache (16-bit or per-tensor INT8 pools): p.C is the
-// host-side cap on every sequence's length, which sizes the split and the workspace
-// (decode_workspace_bytes of that cap).
+// host-side cap on every sequence's length.  The split and the workspace follow
+// decode_paged_span(cap, ...): the cap, or under the causal window (p.mask.causal and
+// p.mask.window, window_size <= 2^30) min(cap, W + R + 31) keys, which the kernels count from
+// the sequence's window base; the workspace is decode_workspace_bytes of that span.
+int decode_paged_span(int cap, int R, bool window, uint32_t window_size);
 hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int elem,
                                      void* workspace, hipStream_t stream);
 // Ragged multi-row forward over the same cache, 16-bit pools of the compute type `elem`

@@ -78,6 +78,7 @@ class Sparsity(enum.IntEnum):
     causal = 1
     slidingWindow = 2
     custom = 3
+    causalWindow = 4   # MFA_SPARSITY_CAUSAL_WINDOW: the paged K/V calls only (no Swift counterpart)
 
 
 class MaskType(enum.IntEnum):
@@ -132,7 +133,14 @@ class AttentionDescriptor(ctypes.Structure):
     @classmethod
     def make(cls, row=None, column=None, head=None, low_precision=False, precision=None,
              low_precision_intermediates=None, causal=False, window=None, scale=None,
-             transpose=(False, False, False, False), sparse_mask: Optional[int] = None):
+             transpose=(False, False, False, False), sparse_mask: Optional[int] = None,
+             causal_window=None):
+        """causal / window: the reference's patterns (window alone or with causal is the
+        one-sided slidingWindow).  causal_window=W: Sparsity.causalWindow, the KV-cache mask
+        t_q - W <= key <= t_q of paged_decode_forward and the two paged prefill calls; it cannot
+        be combined with the other two."""
+        if causal_window is not None and (causal or window is not None):
+            raise ValueError("causal_window excludes causal= and window=")
         d = cls()
         lib.mfa_attention_descriptor_init(ctypes.byref(d))
         if row is not None:
@@ -150,6 +158,9 @@ class AttentionDescriptor(ctypes.Structure):
         if window is not None:
             d.sparsity_pattern = Sparsity.slidingWindow
             d.window_size = window
+        if causal_window is not None:
+            d.sparsity_pattern = Sparsity.causalWindow
+            d.window_size = causal_window
         if scale is not None:
             d.has_softmax_scale = 1
             d.softmax_scale = scale
@@ -854,7 +865,11 @@ def paged_decode_forward(desc: PagedDecodeDescriptor, query, cache: PagedKVCache
                          logsumexp=None, query_strides=None, stream=None):
     """mfa_paged_decode_forward: split-KV decode over a paged, ragged K/V cache.  query
     [B, H, R, D] 16-bit, output FP32 [B, H, R, D]; the lengths and the block table stay on the
-    device, so the call can be captured in a graph and replayed with new values."""
+    device, so the call can be captured in a graph and replayed with new values.
+    Masks: none, causal (row q at key position len - R + q), or
+    AttentionDescriptor.make(causal_window=W): keys t_q - W <= j <= t_q.  Under the window the
+    splits and the workspace follow W + R + 31 keys, not max_seq_len, and pages wholly below
+    max(0, len - R) - W are never read: they may be freed and their table entries left stale."""
     s = _strides(query_strides)
     check(lib.mfa_paged_decode_forward(ctypes.byref(desc), _ptr(query), s[0] if s else None,
                                        ctypes.byref(cache), _ptr(output), _ptr(logsumexp),
@@ -874,7 +889,9 @@ def paged_prefill_forward(desc: PagedPrefillDescriptor, query, cache: PagedKVCac
     append and new_lens (device int32 [B], optional) the rows of each sequence, as for
     paged_kv_append.  Row q < new_lens[b] is key position seq_lens[b] - new_lens[b] + q; other
     rows get zeros.  output FP32 [B, H, R, D].  Nothing is read on the host, so lens += n,
-    append, prefill can be captured in one graph."""
+    append, prefill can be captured in one graph.
+    Masks: none, causal (keys j <= t_q), or AttentionDescriptor.make(causal_window=W): keys
+    t_q - W <= j <= t_q; pages wholly below max(0, seq_lens[b] - new_lens[b]) - W are never read."""
     s = _strides(query_strides)
     check(lib.mfa_paged_prefill_forward(ctypes.byref(desc), _ptr(query), s[0] if s else None,
                                         _ptr(new_lens), ctypes.byref(cache), _ptr(output),
@@ -893,7 +910,8 @@ def quantized_paged_prefill_forward(desc: PagedPrefillDescriptor, query, cache: 
                                     stream=None):
     """mfa_quantized_paged_prefill_forward: paged_prefill_forward over a cache whose pools may be
     per-tensor INT8 (widened on load; cache.k_scale multiplies the softmax scale, cache.v_scale
-    the output, as in paged_decode_forward).  16-bit pools run paged_prefill_forward's kernel."""
+    the output, as in paged_decode_forward).  16-bit pools run paged_prefill_forward's kernel.
+    The masks, causal_window=W and its page-release rule included, are paged_prefill_forward's."""
     s = _strides(query_strides)
     check(lib.mfa_quantized_paged_prefill_forward(
         ctypes.byref(desc), _ptr(query), s[0] if s else None, _ptr(new_lens), ctypes.byref(cache),
