@@ -2028,13 +2028,16 @@ void paged_kv_mask(const mfa_attention_descriptor_t& base, mfa::MaskArgs* m) {
   m->skip_ok = 1;
 }
 
-// Split-KV decode over the cache (attention_decode.hip, the *_paged_kernel entry points).  The
-// split layout, the grid and the partials workspace (library scratch slot 15) follow max_seq_len,
-// or under the causal window the window (decode_paged_span).
-mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void* query,
-                          const int64_t* query_strides, const mfa_paged_kv_cache_t* cache,
-                          float* output, void* logsumexp, hipStream_t stream) {
-  const char* const what = "paged decode";
+// The front end of the paged K/V decode and prefill calls, whose descriptors have the same
+// fields: every host rule in its order, then the forward's parameters.  `limits(B, H, Hkv, R)`
+// is the call's own size rules, applied between the scale rule and the empty call's exit;
+// `launch(p, cv, elem)` its workspace and dispatch.  k_scale folds into the softmax multiplier
+// and v_scale into o_mul; 16-bit pools fold 1 (the same bits as without).
+template <class Desc, class Limits, class Launch>
+mfa_status_t paged_kv_forward(const char* what, const Desc* desc, const void* query,
+                              const int64_t* query_strides, const mfa_paged_kv_cache_t* cache,
+                              float* output, void* logsumexp, hipStream_t stream, bool allow_i8,
+                              Limits limits, Launch launch) {
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const mfa_attention_descriptor_t& base = desc->base;
   const int64_t B = desc->batch_size, H = desc->num_heads, Hkv = desc->num_kv_heads;
@@ -2051,21 +2054,18 @@ mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void*
     return fail(MFA_ERR_UNSUPPORTED, "%s: query precision %d (FP16 or BF16)", what, qprec);
   PagedCacheView cv;
   mfa_status_t st =
-      paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", true, &cv);
+      paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", allow_i8, &cv);
   if (st != MFA_SUCCESS) return st;
   if (!paged_kv_mask_served(base))
     return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal and the causal window", what);
   if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
   const float scale = resolve_scale(base, (int)D);
+  // One rule and one association for decode and prefill: (log2 e · scale) · k_scale, so the two
+  // calls give an INT8 pool the same bits.
   const float fk = cv.i8 ? cache->k_scale : 1.f, fv = cv.i8 ? cache->v_scale : 1.f;
   if (!(scale > 0.f) || !(fk > 0.f) || !(1.442695041f * scale * fk > 0.f))
     return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
-  const int64_t rows = (H / Hkv) * R;
-  if (B * Hkv * ((rows + 31) / 32) >= 65536)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: %lld x %lld x %lld units exceed the grid", what,
-                (long long)B, (long long)Hkv, (long long)((rows + 31) / 32));
-  if (B * H * R >= ((int64_t)1 << 31))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
+  if ((st = limits(B, H, Hkv, R)) != MFA_SUCCESS) return st;
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
   if ((st = paged_cache_buffers(what, *cache, "query, output", query && output)) != MFA_SUCCESS)
     return st;
@@ -2087,15 +2087,39 @@ mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void*
   p.c_log2 = 1.442695041f * scale * fk;
   p.o_mul = fv;
   paged_kv_mask(base, &p.mask);
+  return launch(p, cv, elem);
+}
 
-  void* ws = nullptr;
-  const int span = mfa::decode_paged_span((int)cv.cap, (int)R, p.mask.window, p.mask.window_size);
-  const size_t wsb = mfa::decode_workspace_bytes((int)B, (int)Hkv, (int)rows, span, (int)D);
-  if (wsb && mfa::plan_capture()) ws = (void*)kPlanDummy;
-  else if (wsb && (st = scratch(wsb, &ws, 15, stream)) != MFA_SUCCESS) return st;
-  const hipError_t e = mfa::fwd_decode_paged_dispatch(p, cv.pg, elem, ws, stream);
-  if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
-  return hip_status(e, "mfa_fwd (paged decode) launch");
+// Split-KV decode over the cache (attention_decode.hip, the *_paged_kernel entry points).  The
+// split layout, the grid and the partials workspace (library scratch slot 15) follow max_seq_len,
+// or under the causal window the window (decode_paged_span).
+mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void* query,
+                          const int64_t* query_strides, const mfa_paged_kv_cache_t* cache,
+                          float* output, void* logsumexp, hipStream_t stream) {
+  const char* const what = "paged decode";
+  return paged_kv_forward(
+      what, desc, query, query_strides, cache, output, logsumexp, stream, true,
+      [&](int64_t B, int64_t H, int64_t Hkv, int64_t R) -> mfa_status_t {
+        const int64_t blocks = ((H / Hkv) * R + 31) / 32;
+        if (B * Hkv * blocks >= 65536)
+          return fail(MFA_ERR_UNSUPPORTED, "%s: %lld x %lld x %lld units exceed the grid", what,
+                      (long long)B, (long long)Hkv, (long long)blocks);
+        if (B * H * R >= ((int64_t)1 << 31))
+          return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
+        return MFA_SUCCESS;
+      },
+      [&](const mfa::FwdParams& p, const PagedCacheView& cv, int elem) -> mfa_status_t {
+        void* ws = nullptr;
+        mfa_status_t st;
+        const int span = mfa::decode_paged_span(p.C, p.R, p.mask.window, p.mask.window_size);
+        const size_t wsb = mfa::decode_workspace_bytes(p.B, p.Hkv, p.H / p.Hkv * p.R, span, p.D);
+        if (wsb && mfa::plan_capture()) ws = (void*)kPlanDummy;
+        else if (wsb && (st = scratch(wsb, &ws, 15, stream)) != MFA_SUCCESS) return st;
+        const hipError_t e = mfa::fwd_decode_paged_dispatch(p, cv.pg, elem, ws, stream);
+        if (e == hipErrorNotSupported)
+          return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
+        return hip_status(e, "mfa_fwd (paged decode) launch");
+      });
 }
 
 // The write side (paged_append.hip): new key / value rows to their slots in the pools, addressed
@@ -2172,63 +2196,23 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
                            const mfa_paged_kv_cache_t* cache, float* output, void* logsumexp,
                            hipStream_t stream, bool allow_i8) {
   const char* const what = allow_i8 ? "quantized paged prefill" : "paged prefill";
-  if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
-  const mfa_attention_descriptor_t& base = desc->base;
-  const int64_t B = desc->batch_size, H = desc->num_heads, Hkv = desc->num_kv_heads;
-  const int64_t R = desc->rows, D = desc->head_dim;
-  if (H == 0 || Hkv == 0 || D == 0 || desc->max_seq_len == 0 || cache->max_pages_per_seq == 0 ||
-      cache->num_pages == 0)
-    return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: empty shape", what);
-  if (H % Hkv != 0)
-    return fail(MFA_ERR_INVALID_DESCRIPTOR, "%s: %lld heads over %lld kv heads", what,
-                (long long)H, (long long)Hkv);
-  const int qprec = resolve_precisions(base).mem[MFA_OPERAND_Q];
-  const int elem = elem_of(qprec);
-  if (elem != 1 && elem != 2)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: query precision %d (FP16 or BF16)", what, qprec);
-  PagedCacheView cv;
-  mfa_status_t st =
-      paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", allow_i8, &cv);
-  if (st != MFA_SUCCESS) return st;
-  if (!paged_kv_mask_served(base))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal and the causal window", what);
-  if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
-  const float scale = resolve_scale(base, (int)D);
-  // The decode call's rule and association; 16-bit pools fold 1 (the same bits as without).
-  const float fk = cv.i8 ? cache->k_scale : 1.f, fv = cv.i8 ? cache->v_scale : 1.f;
-  if (!(scale > 0.f) || !(fk > 0.f) || !(1.442695041f * scale * fk > 0.f))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
-  if (B * H * R >= ((int64_t)1 << 31))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
-  if (B * H * ((R + 127) / 128) >= ((int64_t)1 << 31))
-    return fail(MFA_ERR_UNSUPPORTED, "%s: the query blocks exceed the grid", what);
-  if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
-  if ((st = paged_cache_buffers(what, *cache, "query, output", query && output)) != MFA_SUCCESS)
-    return st;
-
-  mfa::FwdParams p;
-  memset(&p, 0, sizeof(p));
-  p.q = make_operand(query, qprec, (int)B, (int)H, (int)R, (int)D, query_strides, 0);
-  if (p.q.sd != 1 || !p.q.vec)
-    return fail(MFA_ERR_UNSUPPORTED, "%s: query rows must be dense and 16-byte aligned", what);
-  paged_pool_operands(*cache, cv, (int)D, &p);
-  p.o = output;
-  out_strides((int)R, (int)D, false, &p.o_ss, &p.o_sd);
-  p.o_sh = R * D;
-  p.o_sb = H * R * D;
-  p.l_f16 = resolve_precisions(base).mem[MFA_OPERAND_L] == MFA_PRECISION_FP16;
-  if ((st = l_or_scratch(logsumexp, B * H * R, stream, &p.l)) != MFA_SUCCESS) return st;
-  p.B = (int)B; p.H = (int)H; p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
-  p.C = (int)cv.cap;
-  p.c_log2 = 1.442695041f * scale * fk;
-  p.o_mul = fv;
-  paged_kv_mask(base, &p.mask);
-
-  const hipError_t e = cv.i8
-                           ? mfa::fwd_prefill_paged_kv8_dispatch(p, cv.pg, new_lens, elem, stream)
-                           : mfa::fwd_prefill_paged_dispatch(p, cv.pg, new_lens, elem, stream);
-  if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
-  return hip_status(e, "mfa_fwd (paged prefill) launch");
+  return paged_kv_forward(
+      what, desc, query, query_strides, cache, output, logsumexp, stream, allow_i8,
+      [&](int64_t B, int64_t H, int64_t, int64_t R) -> mfa_status_t {
+        if (B * H * R >= ((int64_t)1 << 31))
+          return fail(MFA_ERR_UNSUPPORTED, "%s: too many query rows", what);
+        if (B * H * ((R + 127) / 128) >= ((int64_t)1 << 31))
+          return fail(MFA_ERR_UNSUPPORTED, "%s: the query blocks exceed the grid", what);
+        return MFA_SUCCESS;
+      },
+      [&](const mfa::FwdParams& p, const PagedCacheView& cv, int elem) -> mfa_status_t {
+        const hipError_t e =
+            cv.i8 ? mfa::fwd_prefill_paged_kv8_dispatch(p, cv.pg, new_lens, elem, stream)
+                  : mfa::fwd_prefill_paged_dispatch(p, cv.pg, new_lens, elem, stream);
+        if (e == hipErrorNotSupported)
+          return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
+        return hip_status(e, "mfa_fwd (paged prefill) launch");
+      });
 }
 
 // -----------------------------------------------------------------------------------------

@@ -1,7 +1,16 @@
 """Shared helpers for the GPU parity tests (device tensors <-> oracle arrays)."""
 from __future__ import annotations
 
+import functools
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+import types
+
 import numpy as np
+import pytest
 import torch
 
 import mfa_amd as mfa
@@ -436,3 +445,49 @@ def run_forward(Qn, Kn, Vn, prec=mfa.Precision.FP32, causal=False, window=None, 
     mfa.MultiHeadAttention().forward(desc, q, k, v, o, l, mask=mask)
     torch.cuda.synchronize()
     return o, l
+
+
+# ------------------------------------------------------------------ code-object metadata
+_LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                    "metal-flash-attention-plus_amd", "libmfa_amd.so")
+_LLVM = "/opt/rocm/lib/llvm/bin"
+_NOTE_FIELDS = {"scratch": "private_segment_fixed_size", "vgpr_spill": "vgpr_spill_count",
+                "sgpr_spill": "sgpr_spill_count", "vgpr": "vgpr_count",
+                "lds": "group_segment_fixed_size"}
+
+
+@functools.lru_cache(maxsize=None)
+def code_object_metadata():
+    """{mangled kernel name: {"scratch", "vgpr_spill", "sgpr_spill", "vgpr", "lds"}} of every
+    gfx950 kernel in the built library, from the code objects' metadata notes (llvm-objdump
+    --offloading, llvm-readelf --notes; nothing is disassembled).  Extracted once per process,
+    into a temporary directory.  Skips the calling test or fixture where the library or the ROCm
+    LLVM tools are absent.  The result is shared by every caller and read-only."""
+    if not (os.path.exists(_LIB) and os.path.exists(os.path.join(_LLVM, "llvm-readelf"))):
+        pytest.skip("library or ROCm LLVM tools not present")
+    notes = ""
+    with tempfile.TemporaryDirectory() as d:
+        lib = shutil.copy(_LIB, d)
+        subprocess.run([os.path.join(_LLVM, "llvm-objdump"), "--offloading", lib], check=True,
+                       capture_output=True, cwd=d)
+        for f in sorted(os.listdir(d)):
+            if f.endswith("gfx950"):
+                notes += subprocess.run([os.path.join(_LLVM, "llvm-readelf"), "--notes",
+                                         os.path.join(d, f)], check=True, capture_output=True,
+                                        text=True).stdout
+    out = {}
+    for ent in notes.split("- .agpr_count")[1:]:
+        def field(k):
+            m = re.search(r"\." + k + r":\s+(\S+)", ent)
+            return m.group(1) if m else None
+        vals = {k: field(f) for k, f in _NOTE_FIELDS.items()}
+        # A field a kernel's note lacks is left out, so only a test that reads it notices.
+        out[field("name")] = types.MappingProxyType(
+            {k: int(v) for k, v in vals.items() if v is not None})
+    assert out, "no kernel metadata found"
+    return types.MappingProxyType(out)
+
+
+def kernels_named(fragment):
+    """code_object_metadata() of the kernels whose mangled name contains `fragment`."""
+    return {n: k for n, k in code_object_metadata().items() if fragment in n}

@@ -6,14 +6,12 @@ PMC passes; this pins it at build time.  Needs the ROCm LLVM too
 in this image); skipped otherwise."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+from harness import code_object_metadata
+
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(_REPO, "metal-flash-attention-plus_amd", "libmfa_amd.so")
-_LLVM = "/opt/rocm/lib/llvm/bin"
 
 # Mangled-name fragments of the tuned kernels (csrc/attention_fwd_v2.hip, attention_fwd_pipe.hip,
 # attention_fwd_stream.hip,
@@ -44,29 +42,8 @@ EXEMPT = {"mfa_bwd_q_bigd_kernelINS_7Arith16INS_3F16ELi128EEELi128ELi3E": (160, 
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    if not (os.path.exists(_LIB) and os.path.exists(os.path.join(_LLVM, "llvm-readelf"))):
-        pytest.skip("library or ROCm LLVM tools not present")
-    d = tmp_path_factory.mktemp("co")
-    lib = shutil.copy(_LIB, d)
-    subprocess.run([os.path.join(_LLVM, "llvm-objdump"), "--offloading", lib], check=True,
-                   capture_output=True, cwd=d)
-    notes = ""
-    for f in sorted(os.listdir(d)):
-        if f.endswith("gfx950"):
-            notes += subprocess.run([os.path.join(_LLVM, "llvm-readelf"), "--notes",
-                                     os.path.join(d, f)], check=True, capture_output=True,
-                                    text=True).stdout
-    out = {}
-    for ent in notes.split("- .agpr_count")[1:]:
-        def field(k):
-            m = re.search(r"\." + k + r":\s+(\S+)", ent)
-            return m.group(1) if m else None
-        out[field("name")] = {"scratch": int(field("private_segment_fixed_size")),
-                              "vgpr_spill": int(field("vgpr_spill_count")),
-                              "vgpr": int(field("vgpr_count"))}
-    assert out, "no kernel metadata found"
-    return out
+def kernels():
+    return code_object_metadata()
 
 
 def test_hot_kernels_present(kernels):

@@ -7,18 +7,14 @@ test_paged_decode_gpu.py."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 import mfa_amd as mfa
-from harness import paged_cache as cache, paged_cache_full as full
+from harness import kernels_named, paged_cache as cache, paged_cache_full as full
 
 P = mfa.Precision
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(_REPO, "metal-flash-attention-plus_amd", "libmfa_amd.so")
-_LLVM = "/opt/rocm/lib/llvm/bin"
 OK, INVALID_DESCRIPTOR, UNSUPPORTED, INVALID_ARGUMENT = 0, 1, 2, 4  # mfa_status_t
 
 
@@ -215,30 +211,9 @@ def test_empty_shapes_succeed_and_launch_nothing():
 
 
 @pytest.fixture(scope="module")
-def paged_kernels(tmp_path_factory):
-    """Code-object metadata of the paged kernels (llvm-readelf notes, as test_kernel_resources)."""
-    if not (os.path.exists(_LIB) and os.path.exists(os.path.join(_LLVM, "llvm-readelf"))):
-        pytest.skip("library or ROCm LLVM tools not present")
-    d = tmp_path_factory.mktemp("co_paged")
-    lib = shutil.copy(_LIB, d)
-    subprocess.run([os.path.join(_LLVM, "llvm-objdump"), "--offloading", lib], check=True,
-                   capture_output=True, cwd=d)
-    notes = ""
-    for f in sorted(os.listdir(d)):
-        if f.endswith("gfx950"):
-            notes += subprocess.run([os.path.join(_LLVM, "llvm-readelf"), "--notes",
-                                     os.path.join(d, f)], check=True, capture_output=True,
-                                    text=True).stdout
-    out = {}
-    for ent in notes.split("- .agpr_count")[1:]:
-        def field(k):
-            m = re.search(r"\." + k + r":\s+(\S+)", ent)
-            return m.group(1) if m else None
-        if "_paged_kernel" in field("name"):
-            out[field("name")] = {"scratch": int(field("private_segment_fixed_size")),
-                                  "vgpr_spill": int(field("vgpr_spill_count")),
-                                  "vgpr": int(field("vgpr_count"))}
-    return out
+def paged_kernels():
+    """Code-object metadata of the paged kernels (harness.code_object_metadata)."""
+    return kernels_named("_paged_kernel")
 
 
 def test_paged_kernels_use_no_scratch_and_fit_the_register_file(paged_kernels):

@@ -16,25 +16,11 @@ import torch
 
 import mfa_amd as mfa
 import oracle_lib as ol
-from harness import maxerr, to_device
+from harness import to_device
+from paged_rig import DEV, LatentCache, P, i32, mla_check, mla_descriptor, positions, tag
 from test_mla_absorbed_gpu import make_inputs
 
 pytestmark = pytest.mark.gpu
-
-P = mfa.Precision
-DEV = "cuda:0"
-FLT_MAX = float(np.finfo(np.float32).max)
-
-
-def positions(lens, R, causal, cap=None):
-    """Last key every row sees ([B, R], -1: no visible key) under the call's clamp."""
-    out = np.full((len(lens), R), -1, np.int64)
-    for b, c in enumerate(lens):
-        c = min(max(c, 0), cap if cap is not None else max(c, 0))
-        for q in range(R):
-            lim = c - R + q if causal else c - 1
-            out[b, q] = lim if lim >= 0 else -1
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -44,7 +30,7 @@ def problem(B, H, R, D, latent, prec, lens, causal=False, seed=0):
     C = max(max(lens), 1)
     lat, wk, wv, Q = make_inputs(B, H, R, C, D, latent, prec, seed + R + sum(lens))
     lats = [lat.reshape(B, C, latent)[b, :max(c, 0)] for b, c in enumerate(lens)]
-    pos = positions(lens, R, causal)
+    pos = positions(lens, None, R, causal, decode=True)
     O = np.zeros((B, H, R, D), np.float32)
     L = np.zeros((B, H, R), np.float32)
     for b, c in enumerate(lens):
@@ -61,54 +47,10 @@ def problem(B, H, R, D, latent, prec, lens, causal=False, seed=0):
     return Q, lats, wk, wv, O, L, pos
 
 
-class Cache:
-    """Device pool + block table + lengths of one scattered latent cache.  `table_fill`: what the
-    block table holds for the logical pages no sequence owns."""
-
-    def __init__(self, lats, prec, page, lens=None, shuffle=True, spare=3, seed=1, table_fill=0):
-        B, latent = len(lats), lats[0].shape[1]
-        alloc = [x.shape[0] for x in lats]
-        npg = [-(-c // page) for c in alloc]
-        self.max_pages = max(1, max(npg)) + (1 if table_fill else 0)
-        self.num_pages = sum(npg) + spare
-        ids = np.arange(self.num_pages)
-        if shuffle:
-            ids = np.random.default_rng(seed).permutation(self.num_pages)
-        table = np.full((B, self.max_pages), table_fill, np.int32)
-        pool = np.full((self.num_pages, page, latent), np.nan, np.float32)
-        nxt = 0
-        for b in range(B):
-            for j in range(npg[b]):
-                n = min(page, alloc[b] - j * page)
-                pool[ids[nxt], :n] = lats[b][j * page:j * page + n]
-                table[b, j] = ids[nxt]
-                nxt += 1
-        self.pool = to_device(pool, prec)
-        self.table_np = table
-        self.table = torch.from_numpy(table).to(DEV)
-        self.lens = i32(alloc if lens is None else lens)
-        self.prec, self.page, self.latent = prec, page, latent
-
-    def struct(self):
-        return mfa.PagedLatentCache.make(self.prec, self.page, self.max_pages, self.num_pages,
-                                         self.latent, self.pool, self.table, self.lens)
-
-
-def i32(xs):
-    return None if xs is None else torch.tensor(list(xs), dtype=torch.int32, device=DEV)
-
-
-def descriptor(shape, latent, prec, max_seq_len, causal=False, lpi=None):
-    B, H, R, D = shape
-    base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, causal=causal,
-                                        low_precision_intermediates=lpi)
-    return mfa.PagedMLADecodeDescriptor.make(base, B, H, R, D, latent, max_seq_len, prec)
-
-
 def forward(Q, wk, wv, pc, latent, prec, max_seq_len, causal=False, lpi=None):
     """One call on NaN-filled outputs; returns (O, L, launched kernel names)."""
     B, H, R, D = Q.shape
-    desc = descriptor(Q.shape, latent, prec, max_seq_len, causal, lpi)
+    desc = mla_descriptor(Q.shape, latent, prec, max_seq_len, causal, lpi)
     o = torch.full((B, H, R, D), float("nan"), dtype=torch.float32, device=DEV)
     l = torch.full((B, H, R), float("nan"), dtype=torch.float32 if lpi is False else torch.float16,
                    device=DEV)
@@ -119,40 +61,15 @@ def forward(Q, wk, wv, pc, latent, prec, max_seq_len, causal=False, lpi=None):
     return o, l, [r["name"] for r in mfa.last_launches()]
 
 
-def check(o, l, O, L, pos, prec, what=""):
-    """Rows with a visible key: O within 5e-2 (FP16) / 1e-1 (BF16), L within 3e-2 / 1e-1.  The
-    other rows: exact zeros, L = -inf (FP16 storage) or -FLT_MAX (FP32).  No NaN anywhere."""
-    on, ln = o.cpu().numpy(), l.float().cpu().numpy().astype(np.float64)
-    assert not np.isnan(on).any() and not np.isnan(ln).any(), what
-    live = pos >= 0                                   # [B, R]
-    m = np.broadcast_to(live[:, None, :], ln.shape)   # [B, H, R]
-    assert np.count_nonzero(on[~m]) == 0, what
-    if l.dtype == torch.float16:
-        assert np.all(np.isneginf(ln[~m])), what
-    else:
-        assert np.all(ln[~m] == -FLT_MAX), what
-    if not live.any():
-        return
-    tol_o, tol_l = (5e-2, 3e-2) if prec == P.FP16 else (1e-1, 1e-1)
-    eo, el = maxerr(on[m], O[m]), maxerr(ln[m], L.astype(np.float64)[m])
-    print(f"{what}: O err {eo:.3e} (bound {tol_o:.0e}); L err {el:.3e} (bound {tol_l:.0e})")
-    assert np.isfinite(on[m]).all() and np.isfinite(ln[m]).all(), what
-    assert eo < tol_o and el < tol_l, what
-
-
-def tag(prec):
-    return "F16" if prec == P.FP16 else "BF16"
-
-
 def run_case(B, H, R, D, latent, prec, page, lens, causal=False, max_seq_len=None, lpi=None, **kw):
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, causal)
-    cache = Cache(lats, prec, page, **kw)
+    cache = LatentCache(lats, prec, page, **kw)
     msl = max(max(lens), 1) if max_seq_len is None else max_seq_len
     o, l, names = forward(Q, wk, wv, cache.struct(), latent, prec, msl, causal, lpi)
     assert names[1:] == [f"mfa_mla_latent_paged_kernel<{tag(prec)}, {latent}>",
                          f"mfa_mla_latent_merge_kernel<{tag(prec)}, {latent}, 1>"], names
-    check(o, l, O, L, pos, prec,
-          f"B{B} H{H} R{R} D{D} latent {latent} {tag(prec)} page {page} lens {lens} causal {causal}")
+    mla_check(o, l, O, L, pos, prec,
+              f"B{B} H{H} R{R} D{D} latent {latent} {tag(prec)} page {page} lens {lens} causal {causal}")
     return o, l
 
 
@@ -175,7 +92,7 @@ def test_smallest_page_multi_row_causal(gpu):
 @pytest.mark.parametrize("lpi", [None, False], ids=["L-fp16", "L-fp32"])
 def test_dead_rows(gpu, lpi):
     lens, R = (0, 3, 40), 5
-    pos = positions(lens, R, True)
+    pos = positions(lens, None, R, decode=True)
     assert [(p >= 0).sum() for p in pos] == [0, 3, 5] and list(pos[1]) == [-1, -1, 0, 1, 2]
     run_case(3, 4, R, 64, 256, P.FP16, 32, lens, causal=True, lpi=lpi)
 
@@ -184,10 +101,10 @@ def test_dead_rows(gpu, lpi):
 def test_bit_identical_across_pagings(gpu):
     B, H, R, D, latent, prec, lens = 2, 4, 3, 64, 256, P.FP16, (300, 97)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, True)
-    o0, l0, _ = forward(Q, wk, wv, Cache(lats, prec, 32, spare=9, seed=3).struct(), latent, prec,
+    o0, l0, _ = forward(Q, wk, wv, LatentCache(lats, prec, 32, spare=9, seed=3).struct(), latent, prec,
                         300, True)
-    check(o0, l0, O, L, pos, prec, "page 32")
-    o1, l1, _ = forward(Q, wk, wv, Cache(lats, prec, 256, shuffle=False).struct(), latent, prec,
+    mla_check(o0, l0, O, L, pos, prec, "page 32")
+    o1, l1, _ = forward(Q, wk, wv, LatentCache(lats, prec, 256, shuffle=False).struct(), latent, prec,
                         300, True)
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
     # One page per sequence over a dense [B, C_alloc, latent] tensor.
@@ -209,10 +126,10 @@ def test_bit_identical_across_pagings(gpu):
 def test_bit_identical_alone_and_in_a_batch(gpu):
     B, H, R, D, latent, prec, page, lens = 3, 4, 2, 64, 256, P.FP16, 64, (300, 33, 64)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, True)
-    o, l, _ = forward(Q, wk, wv, Cache(lats, prec, page).struct(), latent, prec, 300, True)
-    check(o, l, O, L, pos, prec, "batch")
+    o, l, _ = forward(Q, wk, wv, LatentCache(lats, prec, page).struct(), latent, prec, 300, True)
+    mla_check(o, l, O, L, pos, prec, "batch")
     for b in (0, 2):
-        ob, lb, _ = forward(Q[b:b + 1], wk, wv, Cache(lats[b:b + 1], prec, page, seed=9).struct(),
+        ob, lb, _ = forward(Q[b:b + 1], wk, wv, LatentCache(lats[b:b + 1], prec, page, seed=9).struct(),
                             latent, prec, 300, True)
         assert torch.equal(o[b:b + 1], ob) and torch.equal(l[b:b + 1], lb), b
 
@@ -222,8 +139,8 @@ def test_bit_identical_alone_and_in_a_batch(gpu):
 def test_bit_identical_to_the_dense_route(gpu):
     B, H, R, D, latent, prec, S = 2, 16, 1, 128, 512, P.BF16, 1024
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, (S, S))
-    o, l, names = forward(Q, wk, wv, Cache(lats, prec, 64).struct(), latent, prec, S)
-    check(o, l, O, L, pos, prec, "full lengths")
+    o, l, names = forward(Q, wk, wv, LatentCache(lats, prec, 64).struct(), latent, prec, S)
+    mla_check(o, l, O, L, pos, prec, "full lengths")
     assert names[0] == "mfa_mla_qproj_kernel<BF16>"
     base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec)
     od = torch.full((B, H, R, D), float("nan"), dtype=torch.float32, device=DEV)
@@ -245,22 +162,22 @@ def test_lengths_above_the_cap_are_clamped(gpu):
     B, H, R, D, latent, prec, page = 2, 4, 3, 64, 256, P.FP16, 32
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, (64, 64), True)
     pad = np.full((32, latent), 0.5, np.float32)
-    cache = Cache([np.concatenate([lats[0], pad]), lats[1]], prec, page, lens=(64, 64))
+    cache = LatentCache([np.concatenate([lats[0], pad]), lats[1]], prec, page, lens=(64, 64))
     o, l, _ = forward(Q, wk, wv, cache.struct(), latent, prec, 64, True)
     cache.lens = i32((500, 64))
     o2, l2, _ = forward(Q, wk, wv, cache.struct(), latent, prec, 64, True)
     assert torch.equal(o, o2) and torch.equal(l, l2)
-    check(o2, l2, O, L, pos, prec, "clamped")
+    mla_check(o2, l2, O, L, pos, prec, "clamped")
 
 
 def test_unused_table_entries_may_be_out_of_range(gpu):
     B, H, R, D, latent, prec, page, lens = 2, 4, 1, 64, 256, P.FP16, 32, (200, 31)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens)
-    clean = Cache(lats, prec, page)
+    clean = LatentCache(lats, prec, page)
     o0, l0, _ = forward(Q, wk, wv, clean.struct(), latent, prec, 200)
-    check(o0, l0, O, L, pos, prec, "clean table")
+    mla_check(o0, l0, O, L, pos, prec, "clean table")
     for fill in (-7, clean.num_pages + 5):
-        dirty = Cache(lats, prec, page, table_fill=fill)
+        dirty = LatentCache(lats, prec, page, table_fill=fill)
         assert (dirty.table_np == fill).sum() >= 7     # sequence 1's pages 1.., and the extra column
         o1, l1, _ = forward(Q, wk, wv, dirty.struct(), latent, prec, 200)
         assert torch.equal(o0, o1) and torch.equal(l0, l1), fill
@@ -309,7 +226,7 @@ def test_latent_append_writes_only_its_rows(gpu, prec):
 def test_round_trip_with_the_writer(gpu):
     B, H, R, D, latent, prec, page, lens = 3, 4, 3, 64, 512, P.BF16, 64, (250, 96, 40)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, True, seed=4)
-    cache = Cache(lats, prec, page)
+    cache = LatentCache(lats, prec, page)
     for b in range(B):                                  # the cache before the R new tokens
         for t in range(lens[b] - R, lens[b]):
             cache.pool[int(cache.table_np[b, t // page]), t % page] = float("nan")
@@ -318,7 +235,7 @@ def test_round_trip_with_the_writer(gpu):
     mfa.paged_latent_append(mfa.PagedLatentAppendDescriptor.make(prec, B, R, latent, 256), new_rows,
                             pc)
     o, l, _ = forward(Q, wk, wv, pc, latent, prec, 256, True)
-    check(o, l, O, L, pos, prec, "append -> decode")
+    mla_check(o, l, O, L, pos, prec, "append -> decode")
 
 
 # 10. lens += n, append, decode as one graph, replayed with new device values.
@@ -337,7 +254,7 @@ def test_graph_replay_reads_new_lengths(gpu):
     wk, wv = (to_device((rng.standard_normal((latent, H * D)) * s).astype(np.float32), prec)
               for _ in range(2))
     rows = to_device(rng.standard_normal((B, R, latent)).astype(np.float32), prec)
-    desc = descriptor((B, H, R, D), latent, prec, cap, causal=True)
+    desc = mla_descriptor((B, H, R, D), latent, prec, cap, causal=True)
     adesc = mfa.PagedLatentAppendDescriptor.make(prec, B, R, latent, cap)
     o = torch.empty((B, H, R, D), dtype=torch.float32, device=DEV)
     l = torch.empty((B, H, R), dtype=torch.float16, device=DEV)
@@ -368,7 +285,7 @@ def test_graph_replay_reads_new_lengths(gpu):
                 got.append((o.clone(), l.clone()))
             assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1]), new
             assert not torch.isnan(got[1][0]).any() and not torch.isnan(got[1][1].float()).any()
-            pos = positions([a + b for a, b in zip(before, new)], R, True)
+            pos = positions([a + b for a, b in zip(before, new)], None, R, decode=True)
             dead = torch.from_numpy(pos < 0).to(DEV)[:, None, :].expand(B, H, R)
             assert dead.any() or min(a + b for a, b in zip(before, new)) >= R
             assert torch.count_nonzero(got[1][0][dead]).item() == 0
@@ -382,9 +299,9 @@ def test_graph_replay_reads_new_lengths(gpu):
 def test_launch_log_names_the_plan(gpu, R, lens, nsplit):
     B, H, D, latent, prec, page = 2, 4, 64, 256, P.FP16, 32
     Q, lats, wk, wv, _, _, _ = problem(B, H, R, D, latent, prec, lens, R > 1)
-    cache = Cache(lats, prec, page)
+    cache = LatentCache(lats, prec, page)
     _, _, names = forward(Q, wk, wv, cache.struct(), latent, prec, max(lens), R > 1)
-    plan = mfa.paged_mla_decode_plan(descriptor(Q.shape, latent, prec, max(lens), R > 1),
+    plan = mfa.paged_mla_decode_plan(mla_descriptor(Q.shape, latent, prec, max(lens), R > 1),
                                      cache.struct())
     assert names == [r["name"] for r in plan] and len(plan) == 3, (names, plan)
     assert plan[1]["workgroups"] == -(-H * R // 32) * B * nsplit

@@ -18,26 +18,10 @@ import torch
 import mfa_amd as mfa
 import oracle_lib as ol
 from harness import maxerr, seen, to_device
+from paged_rig import DEV, LatentCache, P, i32, mla_check, mla_descriptor, positions, tag
 from test_mla_absorbed_gpu import make_inputs
-from test_paged_mla_gpu import Cache, check, i32, tag
 
 pytestmark = pytest.mark.gpu
-
-P = mfa.Precision
-DEV = "cuda:0"
-
-
-def positions(lens, new, R, causal, cap=None):
-    """Last key every row sees ([B, R], -1: a dead row) under the call's clamps."""
-    out = np.full((len(lens), R), -1, np.int64)
-    for b, c in enumerate(lens):
-        c = min(max(c, 0), cap if cap is not None else max(c, 0))
-        n = R if new is None else min(max(new[b], 0), R)
-        for q in range(n):
-            t = c - n + q
-            if t >= 0:
-                out[b, q] = t if causal else c - 1
-    return out
 
 
 def oracle(Q, lats, wk, wv, pos):
@@ -74,13 +58,6 @@ def problem(B, H, R, D, latent, prec, lens, new=None, causal=True, seed=0):
     return Q, lats, wk, wv, O, L, pos
 
 
-def descriptor(shape, latent, prec, max_seq_len, causal=True, lpi=None):
-    B, H, R, D = shape
-    base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, causal=causal,
-                                        low_precision_intermediates=lpi)
-    return mfa.PagedMLADecodeDescriptor.make(base, B, H, R, D, latent, max_seq_len, prec)
-
-
 def poisoned(Q, new):
     """Q with NaN in the rows q >= n_b, which the call must never use."""
     if new is None:
@@ -94,7 +71,7 @@ def poisoned(Q, new):
 def forward(Q, wk, wv, pc, latent, prec, max_seq_len, new=None, causal=True, lpi=None):
     """One call on NaN-filled outputs; returns (O, L, launched kernel names)."""
     B, H, R, D = Q.shape
-    desc = descriptor(Q.shape, latent, prec, max_seq_len, causal, lpi)
+    desc = mla_descriptor(Q.shape, latent, prec, max_seq_len, causal, lpi)
     o = torch.full((B, H, R, D), float("nan"), dtype=torch.float32, device=DEV)
     l = torch.full((B, H, R), float("nan"), dtype=torch.float32 if lpi is False else torch.float16,
                    device=DEV)
@@ -108,12 +85,12 @@ def forward(Q, wk, wv, pc, latent, prec, max_seq_len, new=None, causal=True, lpi
 def run_case(B, H, R, D, latent, prec, page, lens, new=None, causal=True, max_seq_len=None,
              lpi=None, **kw):
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, new, causal)
-    cache = Cache(lats, prec, page, **kw)
+    cache = LatentCache(lats, prec, page, **kw)
     msl = max(max(lens), 1) if max_seq_len is None else max_seq_len
     o, l, names = forward(Q, wk, wv, cache.struct(), latent, prec, msl, new, causal, lpi)
     assert len(names) == 3 and names[1] == f"mfa_mla_latent_prefill_kernel<{tag(prec)}, {latent}>"
-    check(o, l, O, L, pos, prec, f"B{B} H{H} R{R} D{D} latent {latent} {tag(prec)} page {page} "
-                                 f"lens {lens} new {new} causal {causal}")
+    mla_check(o, l, O, L, pos, prec, f"B{B} H{H} R{R} D{D} latent {latent} {tag(prec)} page {page} "
+                                     f"lens {lens} new {new} causal {causal}")
     return o, l
 
 
@@ -152,12 +129,12 @@ def test_lengths_above_the_cap_are_clamped(gpu, lpi):
     new = (9, 5)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, (64, 64), new)
     pad = np.full((32, latent), 0.5, np.float32)
-    cache = Cache([np.concatenate([lats[0], pad]), lats[1]], prec, page, lens=(64, 64))
+    cache = LatentCache([np.concatenate([lats[0], pad]), lats[1]], prec, page, lens=(64, 64))
     o, l, _ = forward(Q, wk, wv, cache.struct(), latent, prec, 64, new, lpi=lpi)
     cache.lens = i32((500, 64))
     o2, l2, _ = forward(Q, wk, wv, cache.struct(), latent, prec, 64, new, lpi=lpi)
     assert torch.equal(o, o2) and torch.equal(l, l2)
-    check(o2, l2, O, L, pos, prec, "clamped")
+    mla_check(o2, l2, O, L, pos, prec, "clamped")
 
 
 # 3. Further variants.
@@ -190,10 +167,10 @@ def test_sequence_ends_on_a_page_boundary(gpu):
 def test_bit_identical_across_pagings(gpu):
     B, H, R, D, latent, prec, lens, new = 2, 4, 40, 64, 256, P.FP16, (300, 97), (40, 13)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, new)
-    o0, l0, _ = forward(Q, wk, wv, Cache(lats, prec, 32, spare=9, seed=3).struct(), latent, prec,
+    o0, l0, _ = forward(Q, wk, wv, LatentCache(lats, prec, 32, spare=9, seed=3).struct(), latent, prec,
                         300, new)
-    check(o0, l0, O, L, pos, prec, "page 32")
-    o1, l1, _ = forward(Q, wk, wv, Cache(lats, prec, 256, shuffle=False).struct(), latent, prec,
+    mla_check(o0, l0, O, L, pos, prec, "page 32")
+    o1, l1, _ = forward(Q, wk, wv, LatentCache(lats, prec, 256, shuffle=False).struct(), latent, prec,
                         300, new)
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
     # One page per sequence over a dense [B, C_alloc, latent] tensor.
@@ -214,10 +191,10 @@ def test_bit_identical_across_pagings(gpu):
 def test_bit_identical_alone_and_in_a_batch(gpu, R, new):
     B, H, D, latent, prec, page, lens = 3, 4, 64, 256, P.FP16, 64, (300, 33, 64)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, new)
-    o, l, _ = forward(Q, wk, wv, Cache(lats, prec, page).struct(), latent, prec, 300, new)
-    check(o, l, O, L, pos, prec, "batch")
+    o, l, _ = forward(Q, wk, wv, LatentCache(lats, prec, page).struct(), latent, prec, 300, new)
+    mla_check(o, l, O, L, pos, prec, "batch")
     for b in (0, 2):
-        ob, lb, _ = forward(Q[b:b + 1], wk, wv, Cache(lats[b:b + 1], prec, page, seed=9).struct(),
+        ob, lb, _ = forward(Q[b:b + 1], wk, wv, LatentCache(lats[b:b + 1], prec, page, seed=9).struct(),
                             latent, prec, 300, new[b:b + 1])
         assert torch.equal(o[b:b + 1], ob) and torch.equal(l[b:b + 1], lb), b
 
@@ -228,8 +205,8 @@ def test_bit_identical_alone_and_in_a_batch(gpu, R, new):
 def test_bit_identical_to_the_dense_call(gpu):
     B, H, R, D, latent, prec = 2, 4, 200, 64, 512, P.FP16
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, (R, R), (R, R))
-    o, l, names = forward(Q, wk, wv, Cache(lats, prec, 32).struct(), latent, prec, R, (R, R))
-    check(o, l, O, L, pos, prec, "len = n = R")
+    o, l, names = forward(Q, wk, wv, LatentCache(lats, prec, 32).struct(), latent, prec, R, (R, R))
+    mla_check(o, l, O, L, pos, prec, "len = n = R")
     base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, causal=True)
     od = torch.full((B, H, R, D), float("nan"), dtype=torch.float32, device=DEV)
     ld = torch.full((B, H, R), float("nan"), dtype=torch.float16, device=DEV)
@@ -248,12 +225,12 @@ def test_bit_identical_to_the_dense_call(gpu):
 def test_agrees_with_the_decode_call(gpu):
     B, H, R, D, latent, prec, page, lens = 2, 4, 5, 64, 256, P.FP16, 32, (130, 64)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, None)
-    cache = Cache(lats, prec, page)
+    cache = LatentCache(lats, prec, page)
     o, l, _ = forward(Q, wk, wv, cache.struct(), latent, prec, 130)
-    check(o, l, O, L, pos, prec, "prefill")
+    mla_check(o, l, O, L, pos, prec, "prefill")
     od = torch.full_like(o, float("nan"))
     ld = torch.full_like(l, float("nan"))
-    mfa.paged_mla_decode_forward(descriptor(Q.shape, latent, prec, 130), to_device(Q, prec),
+    mfa.paged_mla_decode_forward(mla_descriptor(Q.shape, latent, prec, 130), to_device(Q, prec),
                                  to_device(wk, prec), to_device(wv, prec), cache.struct(), od,
                                  logsumexp=ld)
     torch.cuda.synchronize()
@@ -266,11 +243,11 @@ def test_agrees_with_the_decode_call(gpu):
 def test_unused_table_entries_may_be_out_of_range(gpu):
     B, H, R, D, latent, prec, page, lens, new = 2, 4, 9, 64, 256, P.FP16, 32, (200, 31), (9, 4)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, new)
-    clean = Cache(lats, prec, page)
+    clean = LatentCache(lats, prec, page)
     o0, l0, _ = forward(Q, wk, wv, clean.struct(), latent, prec, 200, new)
-    check(o0, l0, O, L, pos, prec, "clean table")
+    mla_check(o0, l0, O, L, pos, prec, "clean table")
     for fill in (-7, clean.num_pages + 5):
-        dirty = Cache(lats, prec, page, table_fill=fill)
+        dirty = LatentCache(lats, prec, page, table_fill=fill)
         assert (dirty.table_np == fill).sum() >= 7     # sequence 1's pages 1.., and the extra column
         o1, l1, _ = forward(Q, wk, wv, dirty.struct(), latent, prec, 200, new)
         assert torch.equal(o0, o1) and torch.equal(l0, l1), fill
@@ -281,7 +258,7 @@ def test_round_trip_with_the_writer_and_the_decode_call(gpu):
     B, H, R, D, latent, prec, page = 3, 4, 12, 64, 512, P.BF16, 64
     lens, new = (250, 96, 40), (12, 5, 0)
     Q, lats, wk, wv, O, L, pos = problem(B, H, R, D, latent, prec, lens, new, seed=4)
-    cache = Cache(lats, prec, page)
+    cache = LatentCache(lats, prec, page)
     rows = np.zeros((B, R, latent), np.float32)
     for b in range(B):                                  # the cache before the n_b new tokens
         for q in range(new[b]):
@@ -292,17 +269,17 @@ def test_round_trip_with_the_writer_and_the_decode_call(gpu):
     mfa.paged_latent_append(mfa.PagedLatentAppendDescriptor.make(prec, B, R, latent, 256),
                             to_device(rows, prec), pc, new_lens=dn)
     o, l, _ = forward(Q, wk, wv, pc, latent, prec, 256, new)
-    check(o, l, O, L, pos, prec, "append -> prefill")
+    mla_check(o, l, O, L, pos, prec, "append -> prefill")
     # One decode row per sequence on the same struct: the last key's view of the whole sequence.
     Q1 = np.ascontiguousarray(Q[:, :, :1])
     od = torch.full((B, H, 1, D), float("nan"), dtype=torch.float32, device=DEV)
     ld = torch.full((B, H, 1), float("nan"), dtype=torch.float16, device=DEV)
-    mfa.paged_mla_decode_forward(descriptor(Q1.shape, latent, prec, 256), to_device(Q1, prec),
+    mfa.paged_mla_decode_forward(mla_descriptor(Q1.shape, latent, prec, 256), to_device(Q1, prec),
                                  to_device(wk, prec), to_device(wv, prec), pc, od, logsumexp=ld)
     torch.cuda.synchronize()
     p1 = positions(lens, None, 1, True)
     O1, L1 = oracle(Q1, lats, wk, wv, p1)
-    check(od, ld, O1, L1, p1, prec, "append -> prefill -> decode")
+    mla_check(od, ld, O1, L1, p1, prec, "append -> prefill -> decode")
 
 
 #    ... and lens += n, append, prefill as one graph, replayed with new device values; each replay
@@ -323,7 +300,7 @@ def test_graph_replay_reads_new_lengths_and_rows(gpu):
               for _ in range(2))
     rows_np = seen(rng.standard_normal((B, R, latent)).astype(np.float32), prec)
     q, dwk, dwv, rows = (to_device(x, prec) for x in (Q, wk, wv, rows_np))
-    desc = descriptor((B, H, R, D), latent, prec, cap)
+    desc = mla_descriptor((B, H, R, D), latent, prec, cap)
     adesc = mfa.PagedLatentAppendDescriptor.make(prec, B, R, latent, cap)
     o = torch.empty((B, H, R, D), dtype=torch.float32, device=DEV)
     l = torch.empty((B, H, R), dtype=torch.float16, device=DEV)
@@ -364,7 +341,7 @@ def test_graph_replay_reads_new_lengths_and_rows(gpu):
                 assert lens.tolist() == after
                 got.append((o.clone(), l.clone()))
             assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1]), new
-            check(got[1][0], got[1][1], Oref, Lref, pos, prec, f"replay {before} + {new}")
+            mla_check(got[1][0], got[1][1], Oref, Lref, pos, prec, f"replay {before} + {new}")
     assert torch.equal(pool.cpu().float(), torch.from_numpy(pool_np))
 
 
@@ -374,9 +351,9 @@ def test_launch_log_names_the_plan(gpu, R):
     B, H, D, latent, prec, page, lens = 2, 4, 64, 256, P.FP16, 32, (100, 33)
     new = (R, min(R, 7))
     Q, lats, wk, wv, _, _, _ = problem(B, H, R, D, latent, prec, lens, new)
-    cache = Cache(lats, prec, page)
+    cache = LatentCache(lats, prec, page)
     _, _, names = forward(Q, wk, wv, cache.struct(), latent, prec, max(lens), new)
-    plan = mfa.paged_mla_prefill_plan(descriptor(Q.shape, latent, prec, max(lens)), cache.struct())
+    plan = mfa.paged_mla_prefill_plan(mla_descriptor(Q.shape, latent, prec, max(lens)), cache.struct())
     assert names == [r["name"] for r in plan] and len(plan) == 3, (names, plan)
     assert plan[1]["name"] == "mfa_mla_latent_prefill_kernel<F16, 256>"
     assert plan[1]["workgroups"] == B * -(-H * R // 32)

@@ -7,162 +7,32 @@ is the oracle run once per sequence on the stored (rounded) values, row q's keys
 half-open range [0, t_q + 1); rows with a visible key are compared at the tolerances of
 test_forward_v2_gpu.py::check (the same tile body, the same unit-Gaussian data), the others must
 be exact zeros with L at its floor."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import mfa_amd as mfa
-import oracle_lib as ol
-from harness import TORCH_DTYPE, maxerr, seen, to_device
+from harness import TORCH_DTYPE, to_device
+from paged_rig import DEAD_LENS, DEAD_NEW, DEAD_R, DEV, Cache, P, decode_check, i32, positions
+from paged_rig import prefill_check, prefill_descriptor, prefill_forward, prefill_kernel_name
+from paged_rig import prefill_problem
 
 pytestmark = pytest.mark.gpu
 
-P = mfa.Precision
-DEV = "cuda:0"
-FLT_MAX = float(np.finfo(np.float32).max)
 
-
-def positions(lens, new_lens, R, cap=None):
-    """Key position of every row ([B, R], -1: no visible key) under the call's clamps."""
-    out = np.full((len(lens), R), -1, np.int64)
-    for b, c in enumerate(lens):
-        c = min(max(c, 0), cap if cap is not None else c)
-        n = R if new_lens is None else min(max(new_lens[b], 0), R)
-        for q in range(n):
-            if c > 0 and c - n + q >= 0:
-                out[b, q] = c - n + q
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def problem(B, H, Hkv, R, D, prec, lens, new_lens=None, causal=True, seed=0):
-    """Stored-value Q [B, H, R, D], per-sequence K/V [Hkv, len_b, D], the oracle's O / L and the
-    rows' key positions, computed once per case.  One oracle call per sequence."""
-    rng = np.random.default_rng(seed + R * 13 + sum(lens) + D)
-    Q = seen(rng.standard_normal((B, H, R, D)).astype(np.float32), prec)
-    Ks, Vs = ([seen(rng.standard_normal((Hkv, max(c, 0), D)).astype(np.float32), prec)
-               for c in lens] for _ in range(2))
-    pos = positions(lens, new_lens, R)
-    O = np.zeros((B, H, R, D), np.float32)
-    L = np.zeros((B, H, R), np.float32)
-    for b, c in enumerate(lens):
-        if c <= 0 or not (pos[b] >= 0).any():
-            continue
-        hi = np.where(pos[b] >= 0, (pos[b] + 1) if causal else c, 0).astype(np.uint32)
-        ranges = np.zeros((1, Hkv, R, 2), np.uint32)
-        ranges[0, :, :, 1] = hi[None, :]
-        r = ol.attention(Q[b:b + 1], Ks[b][None], Vs[b][None], ranges=ranges)
-        O[b], L[b] = r["O"][0], r["L"][0]
-    for a in [Q, O, L, pos] + Ks + Vs:
-        a.setflags(write=False)
-    return Q, Ks, Vs, O, L, pos
-
-
-class Cache:
-    """Device pools + block table + lengths of one scattered cache.  `table_fill`: what the block
-    table holds for the logical pages no sequence owns."""
-
-    def __init__(self, Ks, Vs, prec, page, lens=None, shuffle=True, spare=3, seed=1, table_fill=0):
-        B = len(Ks)
-        Hkv, _, D = Ks[0].shape
-        alloc = [k.shape[1] for k in Ks]
-        npg = [-(-c // page) for c in alloc]
-        self.max_pages = max(1, max(npg)) + (1 if table_fill else 0)
-        self.num_pages = sum(npg) + spare
-        ids = np.arange(self.num_pages)
-        if shuffle:
-            ids = np.random.default_rng(seed).permutation(self.num_pages)
-        table = np.full((B, self.max_pages), table_fill, np.int32)
-        pools = []
-        for xs in (Ks, Vs):
-            pool = np.full((self.num_pages, Hkv, page, D), np.nan, np.float32)
-            nxt = 0
-            for b in range(B):
-                for j in range(npg[b]):
-                    n = min(page, alloc[b] - j * page)
-                    pool[ids[nxt], :, :n] = xs[b][:, j * page:j * page + n]
-                    table[b, j] = ids[nxt]
-                    nxt += 1
-            pools.append(to_device(pool, prec))
-        self.k, self.v = pools
-        self.table_np = table
-        self.table = torch.from_numpy(table).to(DEV)
-        self.lens = torch.tensor(alloc if lens is None else lens, dtype=torch.int32, device=DEV)
-        self.prec, self.page, self.Hkv, self.D = prec, page, Hkv, D
-
-    def struct(self):
-        return mfa.PagedKVCache.make(self.prec, self.page, self.max_pages, self.num_pages,
-                                     self.Hkv, self.D, self.k, self.v, self.table, self.lens)
-
-
-def descriptor(shape, Hkv, prec, max_seq_len, causal=True, lpi=None):
-    B, H, R, D = shape
-    base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, causal=causal,
-                                        low_precision_intermediates=lpi)
-    return mfa.PagedPrefillDescriptor.make(base, B, H, R, D, max_seq_len, Hkv=Hkv)
-
-
-def i32(xs):
-    return None if xs is None else torch.tensor(xs, dtype=torch.int32, device=DEV)
-
-
-def forward(Q, pc, Hkv, prec, max_seq_len, new_lens=None, causal=True, q=None, q_strides=None,
-            lpi=None):
+def forward(*args, **kw):
     """One call on NaN-filled outputs; returns (O, L, launched kernel names)."""
-    B, H, R, D = Q.shape
-    desc = descriptor(Q.shape, Hkv, prec, max_seq_len, causal, lpi)
-    q = to_device(Q, prec) if q is None else q
-    o = torch.full((B, H, R, D), float("nan"), dtype=torch.float32, device=DEV)
-    l = torch.full((B, H, R), float("nan"), dtype=torch.float32 if lpi is False else torch.float16,
-                   device=DEV)
-    nl = i32(new_lens)
-    mfa.last_launches()
-    mfa.paged_prefill_forward(desc, q, pc, o, new_lens=nl, logsumexp=l, query_strides=q_strides)
-    torch.cuda.synchronize()
-    return o, l, [r["name"] for r in mfa.last_launches()]
-
-
-def check(o, l, O, L, pos, prec, what=""):
-    """Rows with a visible key: test_forward_v2_gpu.py::check's bounds (O 5e-3 FP16 / 1e-2 BF16
-    absolute; L 7e-3 plus half an FP16 ulp of |L| when L is stored in FP16).  The other rows:
-    exact zeros, L = -inf (FP16) or -FLT_MAX (FP32).  No NaN anywhere."""
-    on, ln = o.cpu().numpy(), l.float().cpu().numpy().astype(np.float64)
-    assert not np.isnan(on).any() and not np.isnan(ln).any(), what
-    live = pos >= 0                                   # [B, R]
-    m = np.broadcast_to(live[:, None, :], ln.shape)   # [B, H, R]
-    dead_o, dead_l = on[~m], ln[~m]
-    assert np.count_nonzero(dead_o) == 0, what
-    if l.dtype == torch.float16:
-        assert np.all(np.isneginf(dead_l)), what
-    else:
-        assert np.all(dead_l == -FLT_MAX), what
-    if not live.any():
-        return
-    tol_o = 5e-3 if prec == P.FP16 else 1e-2
-    eo = maxerr(on[m], O[m])
-    lr = L.astype(np.float64)[m]
-    half_ulp = 0.5 * np.spacing(np.abs(lr).astype(np.float16)).astype(np.float64) \
-        if l.dtype == torch.float16 else 0.0
-    excess = float((np.abs(ln[m] - lr) - (7e-3 + half_ulp)).max())
-    print(f"{what}: O err {eo:.3e} (bound {tol_o:.0e}); L error less its bound {excess:.3e}")
-    assert np.isfinite(on[m]).all() and np.isfinite(ln[m]).all(), what
-    assert eo <= tol_o, what
-    assert excess <= 0, what
-
-
-def kernel_name(prec, D):
-    dp = 64 if D <= 64 else 128 if D <= 128 else 256
-    return f"mfa_paged_prefill_kernel<{'F16' if prec == P.FP16 else 'BF16'}, {dp}, {32 if dp == 256 else 64}>"
+    o, l, log, _ = prefill_forward(*args, **kw)
+    return o, l, [r["name"] for r in log]
 
 
 def run_case(B, H, Hkv, R, D, prec, page, lens, new_lens=None, causal=True, **kw):
-    Q, Ks, Vs, O, L, pos = problem(B, H, Hkv, R, D, prec, lens, new_lens, causal)
+    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, lens, new_lens, causal)
     cache = Cache(Ks, Vs, prec, page, **kw)
     o, l, names = forward(Q, cache.struct(), Hkv, prec, max(max(lens), 1), new_lens, causal)
-    assert names == [kernel_name(prec, D)], names
-    check(o, l, O, L, pos, prec, f"B{B} H{H}/{Hkv} R{R} D{D} page {page} lens {lens} new {new_lens}")
+    assert names == [prefill_kernel_name(prec, D)], names
+    prefill_check(o, l, O, L, pos, prec,
+                  f"B{B} H{H}/{Hkv} R{R} D{D} page {page} lens {lens} new {new_lens}")
     return o, l
 
 
@@ -196,26 +66,23 @@ def test_unmasked(gpu):
     run_case(2, 4, 2, 140, 128, P.FP16, 64, (200, 150), (140, 20), causal=False)
 
 
-# 6. Rows without a visible key.
-DEAD_LENS, DEAD_NEW, DEAD_R = (50, 0, 20, 70, 90), (0, 10, 33, -3, 49), 40
-
-
+# 6. Rows without a visible key (paged_rig.DEAD_LENS / DEAD_NEW).
 @pytest.mark.parametrize("lpi", [None, False], ids=["L-fp16", "L-fp32"])
 def test_dead_rows(gpu, lpi):
     B, H, Hkv, R, D, prec, page = 5, 2, 1, DEAD_R, 64, P.FP16, 32
-    Q, Ks, Vs, O, L, pos = problem(B, H, Hkv, R, D, prec, DEAD_LENS, DEAD_NEW)
+    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, DEAD_LENS, DEAD_NEW)
     # new_lens 0 and -3: no row; seq_lens 0: no key; new_lens 33 > seq_lens 20: rows 0..12 lie
     # before key 0 and rows 33.. are not the sequence's; R + 9 is clamped to R.
     assert [(p >= 0).sum() for p in pos] == [0, 0, 20, 0, R]
     assert pos[2, 13] == 0 and pos[2, 32] == 19 and pos[4, 0] == 50
     o, l, _ = forward(Q, Cache(Ks, Vs, prec, page).struct(), Hkv, prec, 90, DEAD_NEW, lpi=lpi)
-    check(o, l, O, L, pos, prec, f"dead rows lpi={lpi}")
+    prefill_check(o, l, O, L, pos, prec, f"dead rows lpi={lpi}")
 
 
 def test_lengths_above_the_cap_are_clamped(gpu):
     # Caches of 96 and 64 keys, cap 64 (max_seq_len): lengths (500, 64) read as (64, 64).
     B, H, Hkv, R, D, prec, page = 2, 2, 1, 40, 64, P.FP16, 32
-    Q, Ks, Vs, O, L, pos = problem(B, H, Hkv, R, D, prec, (64, 64), (40, 9))
+    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, (64, 64), (40, 9))
     pad = np.full((Hkv, 32, D), 0.5, np.float32)
     cache = Cache([np.concatenate([Ks[0], pad], 1), Ks[1]], [np.concatenate([Vs[0], pad], 1), Vs[1]],
                   prec, page, lens=(64, 64))
@@ -223,15 +90,15 @@ def test_lengths_above_the_cap_are_clamped(gpu):
     cache.lens = i32((500, 64))
     o2, l2, _ = forward(Q, cache.struct(), Hkv, prec, 64, (40, 9))
     assert torch.equal(o, o2) and torch.equal(l, l2)
-    check(o2, l2, O, L, pos, prec, "clamped")
+    prefill_check(o2, l2, O, L, pos, prec, "clamped")
 
 
 # 7. The arithmetic does not depend on the paging.
 def test_bit_identical_across_pagings(gpu):
     B, H, Hkv, R, D, prec, lens, new = 2, 4, 2, 160, 128, P.FP16, (300, 97), (160, 33)
-    Q, Ks, Vs, O, L, pos = problem(B, H, Hkv, R, D, prec, lens, new)
+    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, lens, new)
     o0, l0, _ = forward(Q, Cache(Ks, Vs, prec, 32, spare=9, seed=3).struct(), Hkv, prec, 300, new)
-    check(o0, l0, O, L, pos, prec, "page 32")
+    prefill_check(o0, l0, O, L, pos, prec, "page 32")
     o1, l1, _ = forward(Q, Cache(Ks, Vs, prec, 256, shuffle=False).struct(), Hkv, prec, 300, new)
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
     # One page per sequence over a dense [B, C_alloc, H_kv, D] tensor.
@@ -251,7 +118,7 @@ def test_bit_identical_across_pagings(gpu):
 # 8. ... nor on what else is in the batch.
 def test_bit_identical_alone_and_in_a_batch(gpu):
     B, H, Hkv, R, D, prec, page, lens, new = RAGGED
-    Q, Ks, Vs, _, _, _ = problem(B, H, Hkv, R, D, prec, lens, new)
+    Q, Ks, Vs, _, _, _ = prefill_problem(B, H, Hkv, R, D, prec, lens, new)
     o, l, _ = forward(Q, Cache(Ks, Vs, prec, page).struct(), Hkv, prec, 300, new)
     for b in (0, 2):
         ob, lb, _ = forward(Q[b:b + 1], Cache(Ks[b:b + 1], Vs[b:b + 1], prec, page, seed=9).struct(),
@@ -262,10 +129,10 @@ def test_bit_identical_alone_and_in_a_batch(gpu):
 # 9. Table entries of logical pages no key lies in are never used.
 def test_unused_table_entries_may_be_out_of_range(gpu):
     B, H, Hkv, R, D, prec, page, lens, new = 2, 4, 2, 70, 64, P.FP16, 32, (200, 31), (70, 31)
-    Q, Ks, Vs, O, L, pos = problem(B, H, Hkv, R, D, prec, lens, new)
+    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, lens, new)
     clean = Cache(Ks, Vs, prec, page)
     o0, l0, _ = forward(Q, clean.struct(), Hkv, prec, 200, new)
-    check(o0, l0, O, L, pos, prec, "clean table")
+    prefill_check(o0, l0, O, L, pos, prec, "clean table")
     for fill in (-7, clean.num_pages + 5):
         dirty = Cache(Ks, Vs, prec, page, table_fill=fill)
         assert (dirty.table_np == fill).sum() >= 7     # sequence 1's pages 1.., and the extra column
@@ -276,7 +143,7 @@ def test_unused_table_entries_may_be_out_of_range(gpu):
 # 10. The query as the [B, R, H * D] output of a projection.
 def test_projection_view_of_the_query(gpu):
     B, H, Hkv, R, D, prec, page, lens, new = RAGGED
-    Q, Ks, Vs, _, _, _ = problem(B, H, Hkv, R, D, prec, lens, new)
+    Q, Ks, Vs, _, _, _ = prefill_problem(B, H, Hkv, R, D, prec, lens, new)
     pc = Cache(Ks, Vs, prec, page).struct()
     o0, l0, _ = forward(Q, pc, Hkv, prec, 300, new)
     brhd = to_device(Q, prec).permute(0, 2, 1, 3).contiguous()       # [B, R, H, D]
@@ -288,7 +155,7 @@ def test_projection_view_of_the_query(gpu):
 def test_round_trip_with_the_writer(gpu):
     B, H, Hkv, R, D, prec, page = 3, 4, 2, 96, 128, P.FP16, 64
     lens, new = (250, 96, 40), (96, 96, 7)
-    Q, Ks, Vs, O, L, pos = problem(B, H, Hkv, R, D, prec, lens, new, seed=4)
+    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, lens, new, seed=4)
     # The cache before the chunk: the prefixes scattered by the host, NaN everywhere else.
     cache = Cache(Ks, Vs, prec, page)
     for b in range(B):
@@ -304,7 +171,7 @@ def test_round_trip_with_the_writer(gpu):
     mfa.paged_kv_append(mfa.PagedAppendDescriptor.make(prec, B, Hkv, R, D, 256),
                         to_device(kn, prec), to_device(vn, prec), pc, new_lens=nl)
     o, l, _ = forward(Q, pc, Hkv, prec, 256, new)
-    check(o, l, O, L, pos, prec, "append -> prefill")
+    prefill_check(o, l, O, L, pos, prec, "append -> prefill")
     # The decode call over the same lengths at uniform R = 7: its rows are the last 7 of each chunk.
     Rd = min(new)
     rows = [slice(n - Rd, n) for n in new]
@@ -317,12 +184,7 @@ def test_round_trip_with_the_writer(gpu):
     mfa.paged_decode_forward(mfa.PagedDecodeDescriptor.make(base, B, H, Rd, D, 256, Hkv=Hkv),
                              to_device(qd, prec), pc, od, ld)
     torch.cuda.synchronize()
-    # test_paged_decode_gpu.py::check's bounds.
-    eo, el = maxerr(od, Od), maxerr(ld, Ld)
-    omax, lmax = max(1.0, float(np.abs(Od).max())), float(np.abs(Ld).max())
-    print(f"decode rows: O err {eo:.3e} (bound {2e-3 * omax:.3e}) L err {el:.3e} "
-          f"(bound {7e-3 + 2 ** -11 * lmax:.3e})")
-    assert eo < 2e-3 * omax and el < 7e-3 + 2 ** -11 * lmax
+    decode_check(od, ld, Od, Ld, lens, "decode rows")
 
 
 # 12. lens += n, append, prefill as one graph, replayed with new device values.
@@ -339,7 +201,7 @@ def test_graph_replay_reads_new_lengths_and_rows(gpu):
     pc = mfa.PagedKVCache.make(prec, page, max_pages, num_pages, Hkv, D, k, v, table, lens)
     q, kn, vn = (to_device(rng.standard_normal((B, h, R, D)).astype(np.float32), prec)
                  for h in (H, Hkv, Hkv))
-    desc = descriptor((B, H, R, D), Hkv, prec, cap)
+    desc = prefill_descriptor((B, H, R, D), Hkv, prec, cap)
     adesc = mfa.PagedAppendDescriptor.make(prec, B, Hkv, R, D, cap)
     o = torch.empty((B, H, R, D), dtype=torch.float32, device=DEV)
     l = torch.empty((B, H, R), dtype=torch.float16, device=DEV)
@@ -382,7 +244,7 @@ def test_pool_beyond_2_31_bytes(gpu):
     # 128 KiB pages, 16400 of them (2.1 GiB per pool, untouched but for the used pages): the
     # sequence's three pages are the pool's last three, past a 32-bit byte offset.
     B, H, Hkv, R, D, prec, page, lens, num_pages = 1, 2, 1, 40, 256, P.FP16, 256, (700,), 16400
-    Q, Ks, Vs, O, L, pos = problem(B, H, Hkv, R, D, prec, lens)
+    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, lens)
     pools = []
     for xs in (Ks, Vs):
         pool = torch.empty((num_pages, Hkv, page, D), dtype=TORCH_DTYPE[prec], device=DEV)
@@ -395,16 +257,16 @@ def test_pool_beyond_2_31_bytes(gpu):
     table = torch.tensor([[num_pages - 1, num_pages - 2, num_pages - 3]], dtype=torch.int32, device=DEV)
     pc = mfa.PagedKVCache.make(prec, page, 3, num_pages, Hkv, D, pools[0], pools[1], table, i32(lens))
     o, l, _ = forward(Q, pc, Hkv, prec, lens[0])
-    check(o, l, O, L, pos, prec, "pool beyond 2^31 bytes")
+    prefill_check(o, l, O, L, pos, prec, "pool beyond 2^31 bytes")
 
 
 # 14. What ran is what the plan named.
 def test_launch_log_names_the_plan(gpu):
     for case in (RAGGED, (2, 4, 1, 130, 256, P.FP16, 128, (260, 129), None)):
         B, H, Hkv, R, D, prec, page, lens, new = case
-        Q, Ks, Vs, _, _, _ = problem(B, H, Hkv, R, D, prec, lens, new)
+        Q, Ks, Vs, _, _, _ = prefill_problem(B, H, Hkv, R, D, prec, lens, new)
         cache = Cache(Ks, Vs, prec, page)
         _, _, names = forward(Q, cache.struct(), Hkv, prec, max(lens), new)
-        plan = mfa.paged_prefill_plan(descriptor(Q.shape, Hkv, prec, max(lens)), cache.struct())
+        plan = mfa.paged_prefill_plan(prefill_descriptor(Q.shape, Hkv, prec, max(lens)), cache.struct())
         assert names == [r["name"] for r in plan], (names, plan)
         assert plan[0]["workgroups"] == B * H * -(-R // 128)

@@ -8,127 +8,28 @@ scale * (q - zp), row q's keys the half-open range [0, t_q + 1); the bounds are
 test_paged_prefill_gpu.py::check's, unchanged — the operands after widening are exact, so the
 error sources are the 16-bit kernel's.  Beyond the oracle: the result equals, bit for bit, the
 16-bit call on a pool holding q - zp (power-of-two scales make both foldings exact)."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import mfa_amd as mfa
 import oracle_lib as ol
-import test_paged_prefill_gpu as t16
-from harness import maxerr, seen, to_device
+from harness import seen, to_device
+from paged_rig import DEAD_LENS, DEAD_NEW, DEAD_R, DEV, ZP, Cache, Cache8, P, decode_check, i32
+from paged_rig import positions, prefill8_problem, prefill_check, prefill_descriptor
+from paged_rig import prefill_forward, prefill_kernel_name, prefill_problem
 
 pytestmark = pytest.mark.gpu
-
-P = mfa.Precision
-DEV = "cuda:0"
-ZP = 3
-check, positions, i32 = t16.check, t16.positions, t16.i32
-
-
-def quantise(xs, scale, zp):
-    """test_paged_decode_gpu.py::problem's bytes for one operand's sequences."""
-    return [np.clip(np.rint(x / np.float32(scale)) + zp, -128, 127).astype(np.int8) for x in xs]
-
-
-@functools.lru_cache(maxsize=None)
-def problem(B, H, Hkv, R, D, prec, lens, new_lens=None, causal=True, seed=0, scales=None,
-            zps=(ZP, ZP), oracle=True):
-    """Stored-value Q [B, H, R, D], the bytes of each sequence's K and V [Hkv, len_b, D] with
-    their scales, and (oracle=True) the oracle's O / L on scale * (q - zp), once per sequence."""
-    rng = np.random.default_rng(seed + R * 13 + sum(lens) + D)
-    Q = seen(rng.standard_normal((B, H, R, D)).astype(np.float32), prec)
-    raw = [[rng.standard_normal((Hkv, max(c, 0), D)).astype(np.float32) for c in lens]
-           for _ in range(2)]
-    if scales is None:
-        scales = tuple(float(np.float32(max(float(np.abs(x).max()) for x in xs if x.size) / 120.0))
-                       for xs in raw)
-    qk, qv = (quantise(xs, s, z) for xs, s, z in zip(raw, scales, zps))
-    pos = positions(lens, new_lens, R)
-    O = np.zeros((B, H, R, D), np.float32)
-    L = np.zeros((B, H, R), np.float32)
-    for b, c in enumerate(lens):
-        if not oracle or c <= 0 or not (pos[b] >= 0).any():
-            continue
-        K, V = ((q[b].astype(np.float32) - z) * np.float32(s)
-                for q, s, z in zip((qk, qv), scales, zps))
-        hi = np.where(pos[b] >= 0, (pos[b] + 1) if causal else c, 0).astype(np.uint32)
-        ranges = np.zeros((1, Hkv, R, 2), np.uint32)
-        ranges[0, :, :, 1] = hi[None, :]
-        r = ol.attention(Q[b:b + 1], K[None], V[None], ranges=ranges)
-        O[b], L[b] = r["O"][0], r["L"][0]
-    for a in [Q, O, L, pos] + qk + qv:
-        a.setflags(write=False)
-    return Q, qk, qv, scales, O, L, pos
-
-
-class Cache8:
-    """Device INT8 pools + block table + lengths of one scattered cache.  `fill`: the byte in
-    every slot no sequence owns, or "random"; `table_fill`: what the block table holds for the
-    logical pages no sequence owns."""
-
-    def __init__(self, qk, qv, page, scales, zps=(ZP, ZP), lens=None, shuffle=True, spare=3, seed=1,
-                 fill=0x7f, table_fill=0):
-        B = len(qk)
-        Hkv, _, D = qk[0].shape
-        alloc = [k.shape[1] for k in qk]
-        npg = [-(-c // page) for c in alloc]
-        self.max_pages = max(1, max(npg)) + (1 if table_fill else 0)
-        self.num_pages = sum(npg) + spare
-        ids = np.arange(self.num_pages)
-        if shuffle:
-            ids = np.random.default_rng(seed).permutation(self.num_pages)
-        table = np.full((B, self.max_pages), table_fill, np.int32)
-        pools = []
-        for which, xs in enumerate((qk, qv)):
-            shape = (self.num_pages, Hkv, page, D)
-            if fill == "random":
-                pool = np.random.default_rng(77 + which).integers(-128, 128, shape, dtype=np.int8)
-            else:
-                pool = np.full(shape, fill, np.int8)
-            nxt = 0
-            for b in range(B):
-                for j in range(npg[b]):
-                    n = min(page, alloc[b] - j * page)
-                    pool[ids[nxt], :, :n] = xs[b][:, j * page:j * page + n]
-                    table[b, j] = ids[nxt]
-                    nxt += 1
-            pools.append(torch.from_numpy(pool).to(DEV))
-        self.k, self.v = pools
-        self.table_np = table
-        self.table = torch.from_numpy(table).to(DEV)
-        self.lens = torch.tensor(alloc if lens is None else lens, dtype=torch.int32, device=DEV)
-        self.page, self.Hkv, self.D, self.scales, self.zps = page, Hkv, D, scales, zps
-
-    def struct(self):
-        return mfa.PagedKVCache.make(P.INT8, self.page, self.max_pages, self.num_pages, self.Hkv,
-                                     self.D, self.k, self.v, self.table, self.lens,
-                                     k_scale=self.scales[0], v_scale=self.scales[1],
-                                     k_zero_point=self.zps[0], v_zero_point=self.zps[1])
-
-
-def descriptor(shape, Hkv, prec, max_seq_len, causal=True, lpi=None, scale=None):
-    B, H, R, D = shape
-    base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, causal=causal,
-                                        low_precision_intermediates=lpi, scale=scale)
-    return mfa.PagedPrefillDescriptor.make(base, B, H, R, D, max_seq_len, Hkv=Hkv)
 
 
 def forward(Q, pc, Hkv, prec, max_seq_len, new_lens=None, causal=True, lpi=None, scale=None,
             call=None):
     """One call (the new entry point unless `call` is given) on NaN-filled outputs; returns
     (O, L, launched kernel names).  INT8 caches: the launch log must equal the plan."""
-    B, H, R, D = Q.shape
-    desc = descriptor(Q.shape, Hkv, prec, max_seq_len, causal, lpi, scale)
-    o = torch.full((B, H, R, D), float("nan"), dtype=torch.float32, device=DEV)
-    l = torch.full((B, H, R), float("nan"), dtype=torch.float32 if lpi is False else torch.float16,
-                   device=DEV)
-    mfa.last_launches()
-    (call or mfa.quantized_paged_prefill_forward)(desc, to_device(Q, prec), pc, o,
-                                                  new_lens=i32(new_lens), logsumexp=l)
-    torch.cuda.synchronize()
-    log = mfa.last_launches()
+    B, H, R, _ = Q.shape
+    o, l, log, desc = prefill_forward(Q, pc, Hkv, prec, max_seq_len, new_lens, causal, lpi=lpi,
+                                      scale=scale,
+                                      call=call or mfa.quantized_paged_prefill_forward)
     if call is None and pc.precision == P.INT8:
         plan = mfa.quantized_paged_prefill_plan(desc, pc)
         assert [(r["name"], r["threads"], r["lds_bytes"], r["workgroups"]) for r in log] == \
@@ -138,18 +39,16 @@ def forward(Q, pc, Hkv, prec, max_seq_len, new_lens=None, causal=True, lpi=None,
 
 
 def kernel_name(prec, D):
-    dp = 64 if D <= 64 else 128 if D <= 128 else 256
-    return (f"mfa_paged_prefill_kv8_kernel<{'F16' if prec == P.FP16 else 'BF16'}, {dp}, "
-            f"{32 if dp == 256 else 64}>")
+    return prefill_kernel_name(prec, D, kv8=True)
 
 
 def run_case(B, H, Hkv, R, D, prec, page, lens, new_lens=None, causal=True, lpi=None, **kw):
-    Q, qk, qv, scales, O, L, pos = problem(B, H, Hkv, R, D, prec, lens, new_lens, causal)
+    Q, qk, qv, scales, O, L, pos = prefill8_problem(B, H, Hkv, R, D, prec, lens, new_lens, causal)
     cache = Cache8(qk, qv, page, scales, **kw)
     o, l, names = forward(Q, cache.struct(), Hkv, prec, max(max(lens), 1), new_lens, causal, lpi)
     assert names == [kernel_name(prec, D)], names
-    check(o, l, O, L, pos, prec,
-          f"kv8 B{B} H{H}/{Hkv} R{R} D{D} page {page} lens {lens} new {new_lens} lpi {lpi}")
+    prefill_check(o, l, O, L, pos, prec,
+                  f"kv8 B{B} H{H}/{Hkv} R{R} D{D} page {page} lens {lens} new {new_lens} lpi {lpi}")
     return o, l
 
 
@@ -186,11 +85,11 @@ def test_unmasked(gpu):
 # f. Rows without a visible key.
 @pytest.mark.parametrize("lpi", [None, False], ids=["L-fp16", "L-fp32"])
 def test_dead_rows(gpu, lpi):
-    B, H, Hkv, R, D, prec, page = 5, 2, 1, t16.DEAD_R, 64, P.FP16, 32
-    Q, qk, qv, scales, O, L, pos = problem(B, H, Hkv, R, D, prec, t16.DEAD_LENS, t16.DEAD_NEW)
+    B, H, Hkv, R, D, prec, page = 5, 2, 1, DEAD_R, 64, P.FP16, 32
+    Q, qk, qv, scales, O, L, pos = prefill8_problem(B, H, Hkv, R, D, prec, DEAD_LENS, DEAD_NEW)
     assert [(p >= 0).sum() for p in pos] == [0, 0, 20, 0, R]
-    o, l, _ = forward(Q, Cache8(qk, qv, page, scales).struct(), Hkv, prec, 90, t16.DEAD_NEW, lpi=lpi)
-    check(o, l, O, L, pos, prec, f"kv8 dead rows lpi={lpi}")
+    o, l, _ = forward(Q, Cache8(qk, qv, page, scales).struct(), Hkv, prec, 90, DEAD_NEW, lpi=lpi)
+    prefill_check(o, l, O, L, pos, prec, f"kv8 dead rows lpi={lpi}")
 
 
 # g. The pool is decoded exactly: with power-of-two scales the new call equals, bit for bit, the
@@ -201,8 +100,8 @@ def test_dead_rows(gpu, lpi):
 def test_exact_decode_of_the_pool(gpu, prec, D, vzp):
     B, H, Hkv, R, _, _, page, lens, new = RAGGED
     ks, vs, zps = 2.0 ** -5, 2.0 ** -4, (3, vzp)
-    Q, qk, qv, _, _, _, _ = problem(B, H, Hkv, R, D, prec, lens, new, scales=(ks, vs), zps=zps,
-                                    oracle=False)
+    Q, qk, qv, _, _, _, _ = prefill8_problem(B, H, Hkv, R, D, prec, lens, new, scales=(ks, vs), zps=zps,
+                                             oracle=False)
     assert any((q == (-128 if vzp < 0 else 127)).any() for q in qv)   # the far end of the range
     scale = np.float32(D ** -0.5)
     o8, l8, n8 = forward(Q, Cache8(qk, qv, page, (ks, vs), zps).struct(), Hkv, prec, 300, new,
@@ -210,10 +109,10 @@ def test_exact_decode_of_the_pool(gpu, prec, D, vzp):
     assert n8 == [kernel_name(prec, D)]
     ints = [[q.astype(np.float32) - z for q in qs] for qs, z in zip((qk, qv), zps)]
     assert all(np.array_equal(seen(x, prec), x) for xs in ints for x in xs)   # exact in 16 bits
-    c16 = t16.Cache(ints[0], ints[1], prec, page)
+    c16 = Cache(ints[0], ints[1], prec, page)
     o16, l16, n16 = forward(Q, c16.struct(), Hkv, prec, 300, new,
                             scale=float(scale * np.float32(ks)), call=mfa.paged_prefill_forward)
-    assert n16 == [t16.kernel_name(prec, D)]
+    assert n16 == [prefill_kernel_name(prec, D)]
     assert not torch.isnan(o8).any() and not torch.isnan(l8.float()).any()
     assert torch.equal(o8, o16 * vs)
     assert torch.equal(l8, l16)
@@ -222,9 +121,9 @@ def test_exact_decode_of_the_pool(gpu, prec, D, vzp):
 # h. The arithmetic does not depend on the paging.
 def test_bit_identical_across_pagings(gpu):
     B, H, Hkv, R, D, prec, lens, new = 2, 4, 2, 160, 128, P.FP16, (300, 97), (160, 33)
-    Q, qk, qv, scales, O, L, pos = problem(B, H, Hkv, R, D, prec, lens, new)
+    Q, qk, qv, scales, O, L, pos = prefill8_problem(B, H, Hkv, R, D, prec, lens, new)
     o0, l0, _ = forward(Q, Cache8(qk, qv, 32, scales, spare=9, seed=3).struct(), Hkv, prec, 300, new)
-    check(o0, l0, O, L, pos, prec, "kv8 page 32")
+    prefill_check(o0, l0, O, L, pos, prec, "kv8 page 32")
     o1, l1, _ = forward(Q, Cache8(qk, qv, 256, scales, shuffle=False).struct(), Hkv, prec, 300, new)
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
     # One page per sequence over a dense [B, C_alloc, H_kv, D] tensor.
@@ -246,10 +145,10 @@ def test_bit_identical_across_pagings(gpu):
 #    pages, nor the table entries of logical pages no key lies in.
 def test_nothing_outside_a_sequence_is_read(gpu):
     B, H, Hkv, R, D, prec, page, lens, new = 2, 4, 2, 70, 64, P.FP16, 32, (200, 31), (70, 31)
-    Q, qk, qv, scales, O, L, pos = problem(B, H, Hkv, R, D, prec, lens, new)
+    Q, qk, qv, scales, O, L, pos = prefill8_problem(B, H, Hkv, R, D, prec, lens, new)
     clean = Cache8(qk, qv, page, scales)
     o0, l0, _ = forward(Q, clean.struct(), Hkv, prec, 200, new)
-    check(o0, l0, O, L, pos, prec, "kv8 fill 0x7f")
+    prefill_check(o0, l0, O, L, pos, prec, "kv8 fill 0x7f")
     noisy = Cache8(qk, qv, page, scales, fill="random")
     assert not torch.equal(clean.k, noisy.k) and torch.equal(clean.table, noisy.table)
     o1, l1, _ = forward(Q, noisy.struct(), Hkv, prec, 200, new)
@@ -261,7 +160,7 @@ def test_nothing_outside_a_sequence_is_read(gpu):
         assert torch.equal(o0, o2) and torch.equal(l0, l2), fill
     # The same at D 128, whose chunk geometry differs (16-byte chunks; two segments per tile).
     B, H, Hkv, R, D, prec, page, lens, new = RAGGED
-    Q, qk, qv, scales, _, _, _ = problem(B, H, Hkv, R, D, prec, lens, new)
+    Q, qk, qv, scales, _, _, _ = prefill8_problem(B, H, Hkv, R, D, prec, lens, new)
     a = forward(Q, Cache8(qk, qv, page, scales).struct(), Hkv, prec, 300, new)
     b = forward(Q, Cache8(qk, qv, page, scales, fill="random", table_fill=-7).struct(), Hkv, prec,
                 300, new)
@@ -302,7 +201,7 @@ def test_round_trip_with_the_writer(gpu):
     mfa.paged_kv_append(mfa.PagedAppendDescriptor.make(prec, B, Hkv, R, D, 256),
                         to_device(kn, prec), to_device(vn, prec), pc, new_lens=nl)
     o, l, _ = forward(Q, pc, Hkv, prec, 256, new)
-    check(o, l, O, L, pos, prec, "kv8 append -> prefill")
+    prefill_check(o, l, O, L, pos, prec, "kv8 append -> prefill")
     # The decode call over the same lengths at uniform R = min(new): the last rows of each chunk.
     Rd = min(new)
     rows = [slice(n - Rd, n) for n in new]
@@ -315,12 +214,7 @@ def test_round_trip_with_the_writer(gpu):
     mfa.paged_decode_forward(mfa.PagedDecodeDescriptor.make(base, B, H, Rd, D, 256, Hkv=Hkv),
                              to_device(qd, prec), pc, od, ld)
     torch.cuda.synchronize()
-    # test_paged_decode_gpu.py::check's bounds.
-    eo, el = maxerr(od, Od), maxerr(ld, Ld)
-    omax, lmax = max(1.0, float(np.abs(Od).max())), float(np.abs(Ld).max())
-    print(f"kv8 decode rows: O err {eo:.3e} (bound {2e-3 * omax:.3e}) L err {el:.3e} "
-          f"(bound {7e-3 + 2 ** -11 * lmax:.3e})")
-    assert eo < 2e-3 * omax and el < 7e-3 + 2 ** -11 * lmax
+    decode_check(od, ld, Od, Ld, lens, "kv8 decode rows")
 
 
 # k. lens += n, append, prefill as one linear graph, replayed with new device values.
@@ -338,7 +232,7 @@ def test_graph_replay_reads_new_lengths_and_rows(gpu):
                                k_scale=0.03, v_scale=0.04, k_zero_point=3, v_zero_point=-5)
     q, kn, vn = (to_device(rng.standard_normal((B, h, R, D)).astype(np.float32), prec)
                  for h in (H, Hkv, Hkv))
-    desc = descriptor((B, H, R, D), Hkv, prec, cap)
+    desc = prefill_descriptor((B, H, R, D), Hkv, prec, cap)
     adesc = mfa.PagedAppendDescriptor.make(prec, B, Hkv, R, D, cap)
     o = torch.empty((B, H, R, D), dtype=torch.float32, device=DEV)
     l = torch.empty((B, H, R), dtype=torch.float16, device=DEV)
@@ -381,10 +275,10 @@ def test_graph_replay_reads_new_lengths_and_rows(gpu):
 @pytest.mark.parametrize("prec,D", [(P.FP16, 128), (P.BF16, 64), (P.FP16, 72)])
 def test_16_bit_pools_take_the_siblings_path(gpu, prec, D):
     B, H, Hkv, R, _, _, page, lens, new = RAGGED
-    Q, Ks, Vs, _, _, _ = t16.problem(B, H, Hkv, R, D, prec, lens, new)
-    pc = t16.Cache(Ks, Vs, prec, page).struct()
+    Q, Ks, Vs, _, _, _ = prefill_problem(B, H, Hkv, R, D, prec, lens, new)
+    pc = Cache(Ks, Vs, prec, page).struct()
     o0, l0, n0 = forward(Q, pc, Hkv, prec, 300, new, call=mfa.paged_prefill_forward)
     o1, l1, n1 = forward(Q, pc, Hkv, prec, 300, new)
-    assert n0 == n1 == [t16.kernel_name(prec, D)]
+    assert n0 == n1 == [prefill_kernel_name(prec, D)]
     assert not torch.isnan(o1).any()
     assert torch.equal(o0, o1) and torch.equal(l0, l1)

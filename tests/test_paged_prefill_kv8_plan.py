@@ -7,18 +7,14 @@ anything touches a device, so no GPU is needed.  The GPU twin is test_paged_pref
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 import mfa_amd as mfa
-from harness import paged_cache as cache, paged_cache_full as full
+from harness import kernels_named, paged_cache as cache, paged_cache_full as full
 
 P = mfa.Precision
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(_REPO, "metal-flash-attention-plus_amd", "libmfa_amd.so")
-_LLVM = "/opt/rocm/lib/llvm/bin"
 OK, INVALID_DESCRIPTOR, UNSUPPORTED, INVALID_ARGUMENT = 0, 1, 2, 4  # mfa_status_t
 I8 = dict(prec=P.INT8, k_scale=0.02, v_scale=0.03, k_zero_point=3, v_zero_point=-5)
 
@@ -252,33 +248,10 @@ def test_the_neighbour_still_rejects_quantised_pools():
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    """Code-object metadata of every kernel whose name has `mfa_paged_prefill` in it (llvm-readelf
-    notes, as test_paged_prefill_plan.py reads them)."""
-    if not (os.path.exists(_LIB) and os.path.exists(os.path.join(_LLVM, "llvm-readelf"))):
-        pytest.skip("library or ROCm LLVM tools not present")
-    d = tmp_path_factory.mktemp("co_prefill_kv8")
-    lib = shutil.copy(_LIB, d)
-    subprocess.run([os.path.join(_LLVM, "llvm-objdump"), "--offloading", lib], check=True,
-                   capture_output=True, cwd=d)
-    notes = ""
-    for f in sorted(os.listdir(d)):
-        if f.endswith("gfx950"):
-            notes += subprocess.run([os.path.join(_LLVM, "llvm-readelf"), "--notes",
-                                     os.path.join(d, f)], check=True, capture_output=True,
-                                    text=True).stdout
-    out = {}
-    for ent in notes.split("- .agpr_count")[1:]:
-        def field(k):
-            m = re.search(r"\." + k + r":\s+(\S+)", ent)
-            return m.group(1) if m else None
-        if "mfa_paged_prefill" in field("name"):
-            out[field("name")] = {"scratch": int(field("private_segment_fixed_size")),
-                                  "vgpr_spill": int(field("vgpr_spill_count")),
-                                  "sgpr_spill": int(field("sgpr_spill_count")),
-                                  "vgpr": int(field("vgpr_count")),
-                                  "lds": int(field("group_segment_fixed_size"))}
-    return out
+def kernels():
+    """Code-object metadata of every kernel whose name has `mfa_paged_prefill` in it
+    (harness.code_object_metadata)."""
+    return kernels_named("mfa_paged_prefill")
 
 
 def test_kv8_kernels_use_no_scratch_and_keep_two_workgroups_per_cu(kernels):

@@ -1,9 +1,12 @@
-"""What the three paged entry points (mfa_paged_decode_forward, mfa_paged_prefill_forward,
-mfa_paged_kv_append) return for a call that is wrong in two ways.  They share one cache checker
+"""What the paged K/V entry points (mfa_paged_decode_forward, mfa_paged_prefill_forward,
+mfa_quantized_paged_prefill_forward, mfa_paged_kv_append) return for a call that is wrong in two
+ways.  They share one cache checker
 (PagedCacheView in csrc/mfa_api.cpp), and a shared checker can reorder its callers' checks without
 any single-fault test noticing.  The order pinned here: descriptor nulls, INVALID_DESCRIPTOR
 shape errors, UNSUPPORTED descriptor and cache rules, the empty call's success, null buffers,
-alignment.  Every call is rejected on the host, so no GPU is needed."""
+alignment.  The forwards share one front end as well (paged_kv_forward) and apply their two size
+limits in different orders, pinned per entry point at the end.  Every call is rejected on the
+host, so no GPU is needed."""
 import ctypes
 
 import pytest
@@ -44,13 +47,18 @@ def _prefill_call(d, c, first):
                                              None)
 
 
+def _qprefill_call(d, c, first):
+    return mfa.lib.mfa_quantized_paged_prefill_forward(_ref(d), first, None, None, _ref(c),
+                                                       0x200000, None, None)
+
+
 def _append_call(d, c, first):
     return mfa.lib.mfa_paged_kv_append(_ref(d), first, 0x200000, None, None, None, _ref(c), None)
 
 
 ENTRY = {"decode": (_decode_desc, _decode_call), "prefill": (_prefill_desc, _prefill_call),
-         "append": (_append_desc, _append_call)}
-ALL, FORWARDS = ("decode", "prefill", "append"), ("decode", "prefill")
+         "qprefill": (_prefill_desc, _qprefill_call), "append": (_append_desc, _append_call)}
+ALL, FORWARDS = ("decode", "prefill", "qprefill", "append"), ("decode", "prefill", "qprefill")
 
 
 def _edit(**fields):
@@ -103,3 +111,22 @@ def test_two_faults_return_the_earlier_phases_status(entry, case):
     msg = mfa.lib.mfa_last_error().decode()
     assert st == want, (st, msg)
     assert part in msg, msg
+
+
+# B 65536, H 8, Hkv 2, R 4096: B * H * R = 2^31 query rows, one too many for every forward, and
+# 65536 x 2 x 512 units, too many for decode's grid.  Decode checks its grid first, the prefills
+# the rows (their block count, 2^24 here, can only exceed its limit when the rows do).
+FIRST_LIMIT = {"decode": "units exceed the grid", "prefill": "too many query rows",
+               "qprefill": "too many query rows"}
+
+
+@pytest.mark.parametrize("entry", FORWARDS)
+def test_both_size_limits_broken_returns_the_calls_first(entry):
+    make, call = ENTRY[entry]
+    d = make(B=65536, H=8, Hkv=2, R=4096, D=128)
+    st = call(d, full(d), 0x100000)
+    msg = mfa.lib.mfa_last_error().decode()
+    assert st == UNSUPPORTED, (st, msg)
+    assert FIRST_LIMIT[entry] in msg, msg
+    assert msg.startswith({"decode": "paged decode:", "prefill": "paged prefill:",
+                           "qprefill": "quantized paged prefill:"}[entry]), msg

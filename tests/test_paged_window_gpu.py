@@ -2,8 +2,8 @@
 mfa_paged_decode_forward, mfa_paged_prefill_forward, mfa_quantized_paged_prefill_forward).  Row q
 at key position t_q attends to keys t_q - W <= j <= t_q.  Caches, NaN fill of everything outside
 the sequences (pools, outputs, L), data and tolerances are those of test_paged_decode_gpu.py,
-test_paged_prefill_gpu.py and test_paged_prefill_kv8_gpu.py, whose builders and `check` functions
-are imported unchanged.  The reference is the oracle, once per sequence on the stored values, row
+test_paged_prefill_gpu.py and test_paged_prefill_kv8_gpu.py: the builders and `check` functions
+of paged_rig.py.  The reference is the oracle, once per sequence on the stored values, row
 q's keys given as the sparse range [max(0, t_q - W), t_q + 1).  Beyond the oracle: a window that
 covers everything gives the CAUSAL call's bits, and pages wholly below the window may hold NaN
 and stale table entries (the page-release contract of include/mfa/mfa.h)."""
@@ -15,17 +15,14 @@ import torch
 
 import mfa_amd as mfa
 import oracle_lib as ol
-import test_paged_decode_gpu as dec
-import test_paged_prefill_gpu as t16
-import test_paged_prefill_kv8_gpu as t8
-from harness import maxerr, seen, to_device
+import paged_rig as rig
+from harness import seen, to_device
+from paged_rig import DEAD_LENS, DEAD_NEW, DEAD_R, DEV, NAN, ZP, Cache, Cache8, P, positions
+from paged_rig import cache_of, decode_check, decode_forward, prefill_check
 
 pytestmark = pytest.mark.gpu
 
-P = mfa.Precision
-DEV = "cuda:0"
 HUGE = 2 ** 31 - 1
-NAN = float("nan")
 
 
 def window_ref(Q, Ks, Vs, pos, W):
@@ -49,31 +46,17 @@ def window_ref(Q, Ks, Vs, pos, W):
 
 # ---------------------------------------------------------------------------------- decode
 def decode_positions(lens, R):
-    return np.array([[c - R + q if c - R + q >= 0 else -1 for q in range(R)] for c in lens])
+    return positions(lens, None, R)
 
 
 @functools.lru_cache(maxsize=None)
 def decode_problem(B, H, Hkv, R, D, prec, lens, W, kv8=False):
     """test_paged_decode_gpu.py::problem's data with the window's oracle, once per case."""
-    Q, Ks, Vs, quant, _, _ = dec.problem(B, H, Hkv, R, D, prec, lens, kv8)
+    Q, Ks, Vs, quant, _, _ = rig.decode_problem(B, H, Hkv, R, D, prec, lens, kv8)
     O, L = window_ref(Q, Ks, Vs, decode_positions(lens, R), W)
     O.setflags(write=False)
     L.setflags(write=False)
     return Q, Ks, Vs, quant, O, L
-
-
-def decode_forward(Q, cache, prec, max_seq_len, W=None, causal=False):
-    """One paged decode call on NaN-filled outputs; returns (O, L, launched kernel names)."""
-    B, H, R, D = Q.shape
-    base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, causal=causal,
-                                        causal_window=W)
-    desc = mfa.PagedDecodeDescriptor.make(base, B, H, R, D, max_seq_len, Hkv=cache.Hkv)
-    o = torch.full((B, H, R, D), NAN, dtype=torch.float32, device=DEV)
-    l = torch.full((B, H, R), NAN, dtype=torch.float16, device=DEV)
-    mfa.last_launches()
-    mfa.paged_decode_forward(desc, to_device(Q, prec), cache.struct(), o, l)
-    torch.cuda.synchronize()
-    return o, l, [r["name"] for r in mfa.last_launches()]
 
 
 # (B, H, Hkv, R, D, prec, page, lens, W, max_seq_len)
@@ -89,11 +72,11 @@ SPLIT = (3, 8, 2, 1, 64, P.BF16, 64, (5000, 1600, 700), 1500, 8192)
 def run_decode(case, kv8=False):
     B, H, Hkv, R, D, prec, page, lens, W, msl = case
     Q, Ks, Vs, quant, O, L = decode_problem(B, H, Hkv, R, D, prec, lens, W, kv8)
-    cache = dec.Cache(Ks, Vs, prec, page, quant=quant)
-    o, l, names = decode_forward(Q, cache, prec, msl, W)
-    assert names[0].startswith(dec.kernel_form(H, Hkv, R)), names
+    cache = cache_of(Ks, Vs, prec, page, quant)
+    o, l, names = decode_forward(Q, cache, prec, msl, W=W)
+    assert names[0].startswith(rig.decode_kernel_form(H, Hkv, R)), names
     assert names[0].endswith(", 1>" if kv8 else ", 0>"), names
-    dec.check(o, l, O, L, lens, f"window {case} kv8={kv8} {names}")
+    decode_check(o, l, O, L, lens, f"window {case} kv8={kv8} {names}")
     return o, l, names
 
 
@@ -123,28 +106,28 @@ def test_decode_split_path(gpu, kv8):
 def test_decode_window_zero_returns_the_rows_own_value(gpu):
     B, H, Hkv, R, D, prec, page, lens, _, msl = DEC16
     Q, Ks, Vs, _, O, L = decode_problem(B, H, Hkv, R, D, prec, lens, 0)
-    o, l, _ = decode_forward(Q, dec.Cache(Ks, Vs, prec, page), prec, msl, 0)
+    o, l, _ = decode_forward(Q, Cache(Ks, Vs, prec, page), prec, msl, W=0)
     own = np.stack([np.stack([Vs[b][h % Hkv, lens[b] - R:lens[b]] for h in range(H)])
                     for b in range(B)])
-    dec.check(o, l, own, L, lens, "W = 0 against the stored V rows")
-    dec.check(o, l, O, L, lens, "W = 0 against the oracle")
+    decode_check(o, l, own, L, lens, "W = 0 against the stored V rows")
+    decode_check(o, l, O, L, lens, "W = 0 against the oracle")
     # A second shape with several rows per sequence (32-row form).
     B, H, Hkv, R, D, prec, page, lens, _, msl = DEC32
     Q, Ks, Vs, _, O, L = decode_problem(B, H, Hkv, R, D, prec, lens, 0)
-    o, l, _ = decode_forward(Q, dec.Cache(Ks, Vs, prec, page), prec, msl, 0)
+    o, l, _ = decode_forward(Q, Cache(Ks, Vs, prec, page), prec, msl, W=0)
     own = np.stack([np.stack([Vs[b][h % Hkv, lens[b] - R:lens[b]] for h in range(H)])
                     for b in range(B)])
-    dec.check(o, l, own, L, lens, "W = 0, 40 rows, against the stored V rows")
+    decode_check(o, l, own, L, lens, "W = 0, 40 rows, against the stored V rows")
 
 
 @pytest.mark.parametrize("case,kv8", [(DEC16, False), (DEC16, True), (DEC32, False), (SPLIT, False)],
                          ids=["16rows", "16rows-int8", "32rows", "split"])
 def test_decode_huge_window_is_the_causal_call(gpu, case, kv8):
     B, H, Hkv, R, D, prec, page, lens, _, msl = case
-    Q, Ks, Vs, quant, _, _ = dec.problem(B, H, Hkv, R, D, prec, lens, kv8)
-    cache = dec.Cache(Ks, Vs, prec, page, quant=quant)
+    Q, Ks, Vs, quant, _, _ = rig.decode_problem(B, H, Hkv, R, D, prec, lens, kv8)
+    cache = cache_of(Ks, Vs, prec, page, quant)
     o0, l0, n0 = decode_forward(Q, cache, prec, msl, causal=True)
-    o1, l1, n1 = decode_forward(Q, cache, prec, msl, HUGE)
+    o1, l1, n1 = decode_forward(Q, cache, prec, msl, W=HUGE)
     assert n0 == n1, (n0, n1)
     assert not torch.isnan(o0).any() and not torch.isnan(l0.float()).any()
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
@@ -172,23 +155,23 @@ def release_pages(cache, table_np, lens, los, page):
 def test_decode_pages_below_the_window_are_never_read(gpu, case):
     B, H, Hkv, R, D, prec, page, lens, W, msl = case
     Q, Ks, Vs, _, O, L = decode_problem(B, H, Hkv, R, D, prec, lens, W)
-    cache = dec.Cache(Ks, Vs, prec, page)
-    o0, l0, _ = decode_forward(Q, cache, prec, msl, W)
+    cache = Cache(Ks, Vs, prec, page)
+    o0, l0, _ = decode_forward(Q, cache, prec, msl, W=W)
     los = [max(0, max(0, c - R) - W) for c in lens]
     n = release_pages(cache, cache.table.cpu().numpy(), lens, los, page)
     assert n >= (8 if case is DEC16 else 54 + 1), n
-    o1, l1, _ = decode_forward(Q, cache, prec, msl, W)
+    o1, l1, _ = decode_forward(Q, cache, prec, msl, W=W)
     assert torch.isfinite(o1).all() and torch.isfinite(l1.float()).all()
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
-    dec.check(o1, l1, O, L, lens, f"released pages {case}")
+    decode_check(o1, l1, O, L, lens, f"released pages {case}")
 
 
 def test_decode_graph_replay_moves_the_base(gpu):
     # lens += 1 -> decode as one graph.  W 40, R 1: the base (len - 41) & ~31 is 32 at length 104
     # and 64 from 105 on, so the replays cross the move; sequence 1 crosses a page edge (257).
     B, H, Hkv, R, D, prec, page, cap, W = 2, 8, 2, 1, 128, P.FP16, 32, 320, 40
-    Q, Ks, Vs, _, _, _ = dec.problem(B, H, Hkv, R, D, prec, (cap, cap))
-    cache = dec.Cache(Ks, Vs, prec, page, lens=(103, 255))
+    Q, Ks, Vs, _, _, _ = rig.decode_problem(B, H, Hkv, R, D, prec, (cap, cap))
+    cache = Cache(Ks, Vs, prec, page, lens=(103, 255))
     pc = cache.struct()
     base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, causal_window=W)
     desc = mfa.PagedDecodeDescriptor.make(base, B, H, R, D, cap, Hkv=Hkv)
@@ -227,38 +210,24 @@ def test_decode_graph_replay_moves_the_base(gpu):
             assert torch.equal(o, go) and torch.equal(l, gl), lens
             Kb, Vb = [k_[:, :n] for k_, n in zip(Ks, lens)], [v[:, :n] for v, n in zip(Vs, lens)]
             Or, Lr = window_ref(Q, Kb, Vb, decode_positions(lens, R), W)
-            dec.check(go, gl, Or, Lr, lens, f"replay {lens}")
+            decode_check(go, gl, Or, Lr, lens, f"replay {lens}")
 
 
 # --------------------------------------------------------------------------------- prefill
-def prefill_forward(Q, pc, Hkv, prec, max_seq_len, new_lens=None, W=None, causal=False, lpi=None,
-                    scale=None, call=None):
+def prefill_forward(Q, pc, Hkv, prec, max_seq_len, new_lens=None, W=None, causal=False, **kw):
     """One prefill call on NaN-filled outputs; returns (O, L, launched kernel names)."""
-    B, H, R, D = Q.shape
-    base = mfa.AttentionDescriptor.make(low_precision=True, precision=prec, causal=causal,
-                                        causal_window=W, low_precision_intermediates=lpi,
-                                        scale=scale)
-    desc = mfa.PagedPrefillDescriptor.make(base, B, H, R, D, max_seq_len, Hkv=Hkv)
-    o = torch.full((B, H, R, D), NAN, dtype=torch.float32, device=DEV)
-    l = torch.full((B, H, R), NAN, dtype=torch.float32 if lpi is False else torch.float16,
-                   device=DEV)
-    mfa.last_launches()
-    (call or mfa.paged_prefill_forward)(desc, to_device(Q, prec), pc, o, new_lens=t16.i32(new_lens),
-                                        logsumexp=l)
-    torch.cuda.synchronize()
-    return o, l, [r["name"] for r in mfa.last_launches()]
+    o, l, log, _ = rig.prefill_forward(Q, pc, Hkv, prec, max_seq_len, new_lens, causal, W=W, **kw)
+    return o, l, [r["name"] for r in log]
 
 
 def window_kernel(prec, D, kv8=False):
-    dp = 64 if D <= 64 else 128 if D <= 128 else 256
-    return (f"mfa_paged_window_prefill{'_kv8' if kv8 else ''}_kernel<"
-            f"{'F16' if prec == P.FP16 else 'BF16'}, {dp}, {32 if dp == 256 else 64}>")
+    return rig.prefill_kernel_name(prec, D, kv8, window=True)
 
 
 @functools.lru_cache(maxsize=None)
 def prefill_problem(B, H, Hkv, R, D, prec, lens, new_lens, W):
     """test_paged_prefill_gpu.py::problem's data with the window's oracle, once per case."""
-    Q, Ks, Vs, _, _, pos = t16.problem(B, H, Hkv, R, D, prec, lens, new_lens)
+    Q, Ks, Vs, _, _, pos = rig.prefill_problem(B, H, Hkv, R, D, prec, lens, new_lens)
     O, L = window_ref(Q, Ks, Vs, pos, W)
     O.setflags(write=False)
     L.setflags(write=False)
@@ -276,10 +245,10 @@ D256 = (2, 4, 1, 64, 256, P.BF16, 32, (130, 64), None, 31)
 def run_prefill(case, **kw):
     B, H, Hkv, R, D, prec, page, lens, new, W = case
     Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, lens, new, W)
-    cache = t16.Cache(Ks, Vs, prec, page, **kw)
+    cache = Cache(Ks, Vs, prec, page, **kw)
     o, l, names = prefill_forward(Q, cache.struct(), Hkv, prec, max(lens), new, W)
     assert names == [window_kernel(prec, D)], names
-    t16.check(o, l, O, L, pos, prec, f"window prefill {case}")
+    prefill_check(o, l, O, L, pos, prec, f"window prefill {case}")
     return o, l
 
 
@@ -300,22 +269,22 @@ def test_prefill_small_windows_bf16_d64(gpu, W):
 
 @pytest.mark.parametrize("lpi", [None, False], ids=["L-fp16", "L-fp32"])
 def test_prefill_dead_rows_under_the_window(gpu, lpi):
-    B, H, Hkv, R, D, prec, page, W = 5, 2, 1, t16.DEAD_R, 64, P.FP16, 32, 10
-    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, t16.DEAD_LENS, t16.DEAD_NEW, W)
+    B, H, Hkv, R, D, prec, page, W = 5, 2, 1, DEAD_R, 64, P.FP16, 32, 10
+    Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, DEAD_LENS, DEAD_NEW, W)
     assert [(p >= 0).sum() for p in pos] == [0, 0, 20, 0, R]
-    o, l, _ = prefill_forward(Q, t16.Cache(Ks, Vs, prec, page).struct(), Hkv, prec, 90,
-                              t16.DEAD_NEW, W, lpi=lpi)
-    t16.check(o, l, O, L, pos, prec, f"window dead rows lpi={lpi}")
+    o, l, _ = prefill_forward(Q, Cache(Ks, Vs, prec, page).struct(), Hkv, prec, 90,
+                              DEAD_NEW, W, lpi=lpi)
+    prefill_check(o, l, O, L, pos, prec, f"window dead rows lpi={lpi}")
 
 
 @pytest.mark.parametrize("case", [TWO_BLOCKS, D256], ids=["fp16-128", "bf16-256"])
 def test_prefill_huge_window_is_the_causal_call(gpu, case):
     B, H, Hkv, R, D, prec, page, lens, new, _ = case
-    Q, Ks, Vs, _, _, _ = t16.problem(B, H, Hkv, R, D, prec, lens, new)
-    pc = t16.Cache(Ks, Vs, prec, page).struct()
+    Q, Ks, Vs, _, _, _ = rig.prefill_problem(B, H, Hkv, R, D, prec, lens, new)
+    pc = Cache(Ks, Vs, prec, page).struct()
     o0, l0, n0 = prefill_forward(Q, pc, Hkv, prec, max(lens), new, causal=True)
     o1, l1, n1 = prefill_forward(Q, pc, Hkv, prec, max(lens), new, HUGE)
-    assert n0 == [t16.kernel_name(prec, D)] and n1 == [window_kernel(prec, D)], (n0, n1)
+    assert n0 == [rig.prefill_kernel_name(prec, D)] and n1 == [window_kernel(prec, D)], (n0, n1)
     assert not torch.isnan(o0).any() and not torch.isnan(l0.float()).any()
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
 
@@ -330,14 +299,14 @@ def prefill_los(lens, new, R, W):
 def test_prefill_pages_below_the_window_are_never_read(gpu, case):
     B, H, Hkv, R, D, prec, page, lens, new, W = case
     Q, Ks, Vs, O, L, pos = prefill_problem(B, H, Hkv, R, D, prec, lens, new, W)
-    cache = t16.Cache(Ks, Vs, prec, page)
+    cache = Cache(Ks, Vs, prec, page)
     o0, l0, _ = prefill_forward(Q, cache.struct(), Hkv, prec, max(lens), new, W)
     n = release_pages(cache, cache.table_np, lens, prefill_los(lens, new, R, W), page)
     assert n == (1 if case is TWO_BLOCKS else 11), n
     o1, l1, _ = prefill_forward(Q, cache.struct(), Hkv, prec, max(lens), new, W)
     assert not torch.isnan(o1).any() and not torch.isnan(l1.float()).any()
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
-    t16.check(o1, l1, O, L, pos, prec, f"released pages {case}")
+    prefill_check(o1, l1, O, L, pos, prec, f"released pages {case}")
 
 
 @pytest.mark.parametrize("prec,D", [(P.FP16, 128), (P.FP16, 256), (P.BF16, 64)],
@@ -351,16 +320,16 @@ def test_int8_prefill_is_the_16_bit_window_call_on_the_decoded_pool(gpu, prec, D
     plus the loop bounds (t0, klo, the tile-mask rule) the two kernels share word for word."""
     B, H, Hkv, R, _, _, page, lens, new, W = TWO_BLOCKS
     ks, vs, zps = 2.0 ** -5, 2.0 ** -4, (3, -128)
-    Q, qk, qv, _, _, _, _ = t8.problem(B, H, Hkv, R, D, prec, lens, new, scales=(ks, vs), zps=zps,
-                                       oracle=False)
+    Q, qk, qv, _, _, _, _ = rig.prefill8_problem(B, H, Hkv, R, D, prec, lens, new, scales=(ks, vs),
+                                                 zps=zps, oracle=False)
     scale = np.float32(D ** -0.5)
-    o8, l8, n8 = prefill_forward(Q, t8.Cache8(qk, qv, page, (ks, vs), zps).struct(), Hkv, prec, 300,
+    o8, l8, n8 = prefill_forward(Q, Cache8(qk, qv, page, (ks, vs), zps).struct(), Hkv, prec, 300,
                                  new, W, scale=float(scale),
                                  call=mfa.quantized_paged_prefill_forward)
     assert n8 == [window_kernel(prec, D, kv8=True)], n8
     ints = [[q.astype(np.float32) - z for q in qs] for qs, z in zip((qk, qv), zps)]
     assert all(np.array_equal(seen(x, prec), x) for xs in ints for x in xs)   # exact in 16 bits
-    o16, l16, n16 = prefill_forward(Q, t16.Cache(ints[0], ints[1], prec, page).struct(), Hkv, prec,
+    o16, l16, n16 = prefill_forward(Q, Cache(ints[0], ints[1], prec, page).struct(), Hkv, prec,
                                     300, new, W, scale=float(scale * np.float32(ks)))
     assert n16 == [window_kernel(prec, D)], n16
     assert not torch.isnan(o8).any() and not torch.isnan(l8.float()).any()
@@ -370,11 +339,12 @@ def test_int8_prefill_is_the_16_bit_window_call_on_the_decoded_pool(gpu, prec, D
 
 def test_int8_prefill_against_the_oracle(gpu):
     B, H, Hkv, R, D, prec, page, lens, new, W = TWO_BLOCKS
-    Q, qk, qv, scales, _, _, pos = t8.problem(B, H, Hkv, R, D, prec, lens, new, oracle=False)
-    Ks, Vs = ([(q.astype(np.float32) - t8.ZP) * np.float32(s) for q in qs]
+    Q, qk, qv, scales, _, _, pos = rig.prefill8_problem(B, H, Hkv, R, D, prec, lens, new,
+                                                        oracle=False)
+    Ks, Vs = ([(q.astype(np.float32) - ZP) * np.float32(s) for q in qs]
               for qs, s in zip((qk, qv), scales))
     O, L = window_ref(Q, Ks, Vs, pos, W)
-    o, l, names = prefill_forward(Q, t8.Cache8(qk, qv, page, scales).struct(), Hkv, prec, 300, new,
+    o, l, names = prefill_forward(Q, Cache8(qk, qv, page, scales).struct(), Hkv, prec, 300, new,
                                   W, call=mfa.quantized_paged_prefill_forward)
     assert names == [window_kernel(prec, D, kv8=True)], names
-    t16.check(o, l, O, L, pos, prec, "int8 window prefill")
+    prefill_check(o, l, O, L, pos, prec, "int8 window prefill")
