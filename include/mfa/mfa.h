@@ -851,6 +851,77 @@ mfa_status_t mfa_paged_latent_append_plan(const mfa_paged_latent_append_descript
                                           const mfa_paged_latent_cache_t* cache,
                                           mfa_kernel_plan_t* out);
 
+/* ---------------------------------------------------------------------------------- */
+/* Paged MLA decode with a decoupled RoPE key part next to the latent cache.  (No      */
+/* reference counterpart.)  The score of the MLA models that are deployed has two parts, */
+/*   s(q, j) = scale * (q_nope * W_k,h^T * c_j  +  q_pe * k_pe_j):                       */
+/* c_j is the cached latent row, which W_k absorbs, and k_pe_j a RoPE'd key row that it   */
+/* cannot absorb (the rotation depends on the position), stored once per key and shared   */
+/* by every head.  It enters Q*K^T as rope_dim more contraction dimensions; P*V and W_v    */
+/* see the latent alone.                                                                 */
+
+/* The RoPE'd key part of an MLA cache: one row of rope_dim elements per key, shared by every head.
+ * Pages, block table, lengths, page size and num_pages are the latent cache's.  A second view onto
+ * the same pages, so one struct serves two layouts.  Fused rows [latent | rope] with token stride
+ * latent + 64: pool = the latent pool + latent elements, both strides the latent cache's.
+ * Separate pool: a pool with strides of its own.  Rules: the pool is in the descriptor's
+ * `precision` and 16-byte aligned; strides >= 0 and multiples of 16 bytes; token stride >= rope_dim
+ * elements and below 2^24 bytes; rope_dim other than 64: MFA_ERR_UNSUPPORTED. */
+typedef struct mfa_paged_rope_cache {
+  const void* pool;      /* key in page p, slot s, element d at p*strides[0] + s*strides[1] + d */
+  int64_t strides[2];    /* page, token slot — element strides; d contiguous */
+  uint32_t rope_dim;     /* 64 */
+} mfa_paged_rope_cache_t;
+
+/* mfa_paged_mla_decode_forward with the rope part.  `desc` is that call's descriptor; head_dim is
+ * the no-RoPE width, the one w_k and w_v have.  q_rope: dense [B, H, R, 64] in `precision`, already
+ * rotated by the caller, as the rope rows in the cache are.  Same result as attention with
+ * K_h = [latent * W_k,h | k_rope], Q_h = [query | q_rope], V_h = latent * W_v,h, up to the 16-bit
+ * rounding of Q * W_k^T.  The softmax scale is the base descriptor's, or
+ * 1 / sqrt(head_dim + rope_dim).  Lengths, both masks (NONE, and CAUSAL in the KV-cache
+ * convention), rows with no visible key, clamps, safety rules, limits, scratch and stream / graph
+ * behaviour are mfa_paged_mla_decode_forward's, and a rope row is fetched under the latent row's
+ * rules: none at or past len_b, none from a page the table does not name for the keys read.  NULL
+ * q_rope, rope or rope->pool: MFA_ERR_INVALID_ARGUMENT where the other buffers are checked (a
+ * given rope struct is checked with the cache struct).
+ * Three launches, as that call: its query projection, the latent-space attention with one more
+ * MFMA k-step per wave for the rope dimensions (the rope rows go from global memory straight into
+ * the operand registers, a tile ahead), and the unchanged merge that applies W_v.  With a zero
+ * q_rope the result is mfa_paged_mla_decode_forward's bit for bit at the same scale.
+ * Out of scope: applying the rotation; a prefill call with a rope part; the dense
+ * mfa_mla_forward_absorbed; rope widths other than 64; quantised pools. */
+mfa_status_t mfa_paged_mla_rope_decode_forward(const mfa_paged_mla_descriptor_t* desc,
+                                               const void* query, const void* q_rope,
+                                               const void* w_k, const void* w_v,
+                                               const mfa_paged_latent_cache_t* cache,
+                                               const mfa_paged_rope_cache_t* rope,
+                                               float* output, void* logsumexp, void* stream);
+/* The kernels that call launches (see mfa_multihead_plan).  cache == NULL plans a cache of
+ * 256-key pages in `precision`, rope == NULL a separate dense rope pool over the same pages; NULL
+ * pointers inside either plan aligned buffers. */
+mfa_status_t mfa_paged_mla_rope_decode_plan(const mfa_paged_mla_descriptor_t* desc,
+                                            const mfa_paged_latent_cache_t* cache,
+                                            const mfa_paged_rope_cache_t* rope,
+                                            mfa_kernel_plan_t* out);
+
+/* mfa_paged_latent_append for both parts of a new token: that call's contract with two sources
+ * and two destinations.  k_rope: [B, R, 64] in `precision` with {batch, row} strides under the
+ * latent's rules (k_rope_strides NULL = contiguous).  Both rows go to slot t of the same page in
+ * one launch, the bits unchanged; nothing but the latent and the 64 rope elements of a written
+ * row is touched — with fused rows, the two parts of one row.  NULL k_rope, rope or rope->pool:
+ * MFA_ERR_INVALID_ARGUMENT where the other buffers are checked.  Valid under stream capture. */
+mfa_status_t mfa_paged_latent_rope_append(const mfa_paged_latent_append_descriptor_t* desc,
+                                          const void* latent, const int64_t* latent_strides,
+                                          const void* k_rope, const int64_t* k_rope_strides,
+                                          const int32_t* new_lens,
+                                          const mfa_paged_latent_cache_t* cache,
+                                          const mfa_paged_rope_cache_t* rope, void* stream);
+/* The kernel that call launches (see mfa_paged_mla_rope_decode_plan for NULL structs). */
+mfa_status_t mfa_paged_latent_rope_append_plan(const mfa_paged_latent_append_descriptor_t* desc,
+                                               const mfa_paged_latent_cache_t* cache,
+                                               const mfa_paged_rope_cache_t* rope,
+                                               mfa_kernel_plan_t* out);
+
 /* GPU runtime quantization (GEMMQuantization.swift:305-623 semantics, bit-exact; the
  * reference does this on the CPU in QuantizedTensor.from, :720-860).
  * input: device tensor of `count` elements in `input_precision` (FP32/FP16/BF16), viewed as

@@ -319,6 +319,206 @@ __global__ void __launch_bounds__(256, 2) mfa_mla_latent_paged_kernel(LatentPage
   if (wave == 0 && hh == 0) p.mlpart[prow] = make_float2(m, lp);
 }
 
+// The paged kernel with a decoupled RoPE key part next to the latent
+// (mfa_paged_mla_rope_decode_forward): s(q, j) = Q̃_q·c_j + q_pe_q·k_pe_j, the PV product over
+// the latent alone, so the partial state and the merge are the paged kernel's.  The 64 rope
+// dimensions are one more contraction slice, and they take a path of their own because the
+// latent path has no LDS byte and (at latent 512) hardly a register to give:
+//   * wave w owns rope dims [16w, 16w + 16): one more 32x32x16 MFMA k-step into its partial Sᵀ
+//     before the exchange, whose fixed summation order and the softmax behind it are untouched;
+//   * that k-step's key operand is "key row l32, eight elements at 16w + 8·hh" — one 16-byte
+//     load per lane from the rope row of key t + l32, taken straight from global memory into the
+//     operand registers (`krf`), never through LDS.  The buffer is the tile's page base under the
+//     rope strides, spanning the rows below len_b up to the last one's end, so a row at or past
+//     len_b returns zeros without a fetch as the latent staging does; the page is the block-table
+//     entry the tile's latent rows came from;
+//   * the fragment of tile t + 32 is requested in tile t, after the exchange sum, when the 64
+//     `part` registers are dead: its latency hides under the softmax and the PV MFMAs, and its
+//     four registers stay off the peak.  The descriptor (four SGPRs) is formed where the next
+//     tile's latent loads are issued;
+//   * the q_rope fragment (row r, the same eight elements) is resident like qf; a row past R is
+//     zeros.  With a zero q_rope the extra k-step adds exact zeros and the call is the paged
+//     kernel's bit for bit.
+template <class E, int LAT>
+__global__ void __launch_bounds__(256, 2)
+    mfa_mla_latent_paged_rope_kernel(LatentPagedRopeParams pr) {
+  constexpr int BK = 32, NT = 256;
+  constexpr int WS = LAT / 4;              // latent dims per wave
+  constexpr int DS = WS / 16;              // MFMA k-steps of the wave's QK^T slice
+  constexpr int ND = WS / 32;              // O^T tiles per wave
+  constexpr int CPR = LAT / 8;             // 16-byte chunks per latent row
+  constexpr int CPT = BK * CPR / NT;       // chunks staged per thread
+  constexpr int TILEB = BK * LAT * 2;
+  constexpr int XST = 16;                  // floats per lane in the exchange area
+  constexpr int ROPE = 64;                 // rope elements per key, 16 per wave
+  using A = Arith16<E, LAT>;
+  using TT = Tile16<LAT>;
+  const LatentPagedParams& pp = pr.c;
+  const LatentParams& p = pp.l;
+  const PagedKv& pg = pp.pg;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const tb0 = smem;                              // 2 latent tiles
+  float* const xb = reinterpret_cast<float*>(smem + 2 * TILEB);  // [4 waves][64 lanes][XST]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int split = blockIdx.x % p.nsplit;
+  const int bq = blockIdx.x / p.nsplit;
+  const int b = bq / p.nblk;
+  const int r0 = (bq % p.nblk) * 32;
+  const int r = r0 + l32;
+  const bool rvalid = r < p.R;
+  const int spos = rvalid ? r % p.Sq : 0;   // the row's index among its head's Sq rows
+
+  // The sequence's keys (uniform) and the last key this row sees.
+  const int len = min(max(((latent_i32_ptr)pg.seq_lens)[b], 0), p.Skv);
+  const int klim = p.causal ? len - p.Sq + spos : len - 1;
+
+  // Keys this block needs: all of the sequence, or up to its rows' largest limit.
+  int kend = len;
+  if (p.causal) {
+    const int rl = min(r0 + 31, p.R - 1);
+    const int smax = (r0 / p.Sq == rl / p.Sq) ? rl % p.Sq : p.Sq - 1;
+    kend = min(kend, len - p.Sq + smax + 1);
+  }
+  const int kbeg = split * p.chunk;
+  kend = min(kend, kbeg + p.chunk);
+
+  // Q̃ fragments of the wave's slice: d = w·WS + 16·ds + 8·hh + j.
+  i16x8 qf[DS];
+  {
+    const uint16_t* qrow = (const uint16_t*)p.q + ((int64_t)b * p.R + (rvalid ? r : 0)) * LAT;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) {
+      i16x8 v = i16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (rvalid) v = *reinterpret_cast<const i16x8*>(qrow + wave * WS + 16 * ds + 8 * hh);
+      qf[ds] = v;
+    }
+  }
+  // The q_rope fragment: d = 16·w + 8·hh + j of row r of the dense [B][R][64] rope query, read
+  // through a buffer over the block's rows below R (a row past R returns zeros).
+  const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)((const char*)pr.q_rope + ((int64_t)b * p.R + r0) * (ROPE * 2)), (short)0,
+      min(32, p.R - r0) * (ROPE * 2), 0x00020000);
+  auto qrope_load = [&]() {
+    return __builtin_bit_cast(
+        i16x8, __builtin_amdgcn_raw_buffer_load_b128(qrs, l32 * (ROPE * 2) + 32 * wave + 16 * hh,
+                                                     0, 0));
+  };
+
+  // Block-table entry of the tile at key t (uniform), as stored; the lookup stays in the
+  // sequence's table row (the look-ahead runs past the last tile).
+  const latent_i32_ptr trow = (latent_i32_ptr)pg.block_table + (int64_t)b * pg.max_pages;
+  auto entry = [&](int t) { return trow[min(t >> pg.lg_page, pg.max_pages - 1)]; };
+  const int pmask = (1 << pg.lg_page) - 1;
+  // A tile is one buffer over its page rows below len_b (up to the last such row's end): a
+  // 16-byte load of a row at or past len_b lies outside it and returns zeros without a fetch.
+  // The token strides are below 2^24 bytes, so a tile's row offsets fit the 32-bit buffer offset.
+  const int tokb = (int)pp.tok_bytes;
+  const int voff0 = (tid / CPR) * tokb + 16 * (tid % CPR);   // chunk i: row tid / CPR + i·NT / CPR
+  const int vstep = (NT / CPR) * tokb;
+  const int rtokb = (int)pr.rope_tok_bytes;
+  const int roff = l32 * rtokb + 32 * wave + 16 * hh;        // key row l32, elements 16w + 8hh
+  uint4 stg[CPT];
+  // The rope rows of the tile at key t in page entry `ent`: the same page and slots under the
+  // rope strides, the same row count.
+  auto rope_rsrc = [&](int t, int ent, bool wanted) {
+    const int page = min(max(ent, 0), pg.num_pages - 1);
+    const char* const base = (const char*)pr.rope + (int64_t)page * pr.rope_page_bytes +
+                             (int64_t)(t & pmask) * pr.rope_tok_bytes;
+    const int rows = wanted ? min(len - t, BK) : 0;   // 0: an empty buffer, nothing is fetched
+    const int nb = rows > 0 ? (rows - 1) * rtokb + ROPE * 2 : 0;
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, nb, 0x00020000);
+  };
+  auto rope_load = [&](__amdgpu_buffer_rsrc_t rs) {
+    return __builtin_bit_cast(i16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, roff, 0, 0));
+  };
+  auto load = [&](int t, int ent) {
+    const int page = min(max(ent, 0), pg.num_pages - 1);
+    const char* const base = (const char*)p.lat + (int64_t)page * pg.page_bytes +
+                             (int64_t)(t & pmask) * pp.tok_bytes;
+    const int nb = (min(len - t, BK) - 1) * tokb + LAT * 2;
+    // Chunk i's rows lie i·NT / CPR rows further on: the step goes into the descriptor (scalar
+    // registers, free after the load issues), not into a lane offset of its own — this kernel has
+    // no vector register to spare for CPT - 1 more offsets.
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)(base + i * vstep), (short)0, max(nb - i * vstep, 0), 0x00020000);
+      stg[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff0, 0, 0));
+    }
+  };
+  auto store = [&](char* tile) {
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int id = tid + NT * i;
+      *reinterpret_cast<uint4*>(tile + TT::off(id / CPR, id % CPR)) = stg[i];
+    }
+  };
+
+  f32x16 o[ND];
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt) o[dt] = zero16();
+  float m = -kFltMax, lh = 0.f;
+  const float c = p.c_log2;
+
+  int ent_next = 0;
+  // The rope operands of the tile about to be computed.
+  i16x8 krf = i16x8{0, 0, 0, 0, 0, 0, 0, 0}, qrf = krf;
+  if (kbeg < kend) {
+    const int ent = entry(kbeg);
+    load(kbeg, ent);
+    krf = rope_load(rope_rsrc(kbeg, ent, true));
+    qrf = qrope_load();
+    store(tb0);
+    ent_next = entry(kbeg + BK);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int t = kbeg; t < kend; t += BK) {
+    const bool has_next = t + BK < kend;
+    // The rope k-step opens the tile's partial Sᵀ, ahead of the next tile's staging loads: its
+    // wait is for the one fragment requested a tile ago, not for the loads issued below.
+    const f32x16 sp_rope = A::mma(krf, qrf, zero16());
+    if (has_next) load(t + BK, ent_next);
+    // Scalar work only; without a next tile the buffer is empty and the request below a no-op.
+    const __amdgpu_buffer_rsrc_t rrs_next = rope_rsrc(t + BK, ent_next, has_next);
+    ent_next = entry(t + 2 * BK);
+    const char* kt = tb0 + cur * TILEB;
+
+#define MLA_TILE_LEN len
+#define MLA_TILE_KLIM klim
+#define MLA_TILE_ROPE_SP sp_rope
+#define MLA_TILE_ROPE_FETCH()              \
+  asm volatile("" : "+v"(s) : : "memory"); \
+  krf = rope_load(rrs_next)
+#include "mla_latent_tile_body.h"
+    if (has_next) store(tb0 + (cur ^ 1) * TILEB);
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // Partial state of this key split: Õ unnormalised, (m, l) for the merge pass; the empty state
+  // for a row that saw no key here.
+  float lp = cross_half_sum(lh);
+  if (klim < kbeg) {
+    m = -kFltMax;
+    lp = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt) o[dt] = zero16();
+  }
+  if (!rvalid) return;
+  const int64_t prow = ((int64_t)b * p.nsplit + split) * p.R + r;
+  float* op = p.opart + prow * LAT + wave * WS;
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      *reinterpret_cast<float4*>(op + dt * 32 + 8 * g + 4 * hh) =
+          make_float4(o[dt][4 * g], o[dt][4 * g + 1], o[dt][4 * g + 2], o[dt][4 * g + 3]);
+  if (wave == 0 && hh == 0) p.mlpart[prow] = make_float2(m, lp);
+}
+
 // Ragged prompt chunks over the paged latent cache (mfa_paged_mla_prefill_forward): the paged
 // kernel's staging and addressing, the dense kernel's non-split epilogue (l += FLT_MIN, Õ
 // normalised and rounded to E, L = m + log2 l), and rows that differ per sequence:
@@ -654,6 +854,19 @@ static hipError_t launch_latent_paged(const LatentPagedParams& p, hipStream_t st
   return launch(mfa_mla_latent_merge_kernel<E, LAT, 1>, dim3(l.B * l.R), dim3(MNT), 0, stream, l);
 }
 
+// The paged route with the rope key part: the rope kernel's partials, the same merge.
+template <class E, int LAT>
+static hipError_t launch_latent_paged_rope(const LatentPagedRopeParams& p, hipStream_t stream) {
+  constexpr int LDS = 2 * 32 * LAT * 2 + 4 * 64 * 16 * 4;
+  const LatentParams& l = p.c.l;
+  if (!l.opart || !l.mlpart || !l.wv || l.nsplit < 1 || !p.rope || !p.q_rope)
+    return hipErrorInvalidValue;
+  hipError_t e = launch(mfa_mla_latent_paged_rope_kernel<E, LAT>,
+                        dim3(l.nblk * l.B * l.nsplit), dim3(256), LDS, stream, p);
+  if (e != hipSuccess) return e;
+  return launch(mfa_mla_latent_merge_kernel<E, LAT, 1>, dim3(l.B * l.R), dim3(MNT), 0, stream, l);
+}
+
 // The paged prefill: one launch, the latent-space output left in l.olat for the output GEMM.
 template <class E, int LAT>
 static hipError_t launch_latent_prefill(const LatentPrefillParams& p, hipStream_t stream) {
@@ -762,6 +975,15 @@ hipError_t mla_latent_paged_dispatch(const LatentPagedParams& p, int elem, int l
   return hipErrorNotSupported;
 }
 
+hipError_t mla_latent_paged_rope_dispatch(const LatentPagedRopeParams& p, int elem, int lat,
+                                          hipStream_t stream) {
+  if (lat == 512 && elem == P_FP16) return launch_latent_paged_rope<F16, 512>(p, stream);
+  if (lat == 512 && elem == P_BF16) return launch_latent_paged_rope<BF16, 512>(p, stream);
+  if (lat == 256 && elem == P_FP16) return launch_latent_paged_rope<F16, 256>(p, stream);
+  if (lat == 256 && elem == P_BF16) return launch_latent_paged_rope<BF16, 256>(p, stream);
+  return hipErrorNotSupported;
+}
+
 hipError_t mla_latent_prefill_dispatch(const LatentPrefillParams& p, int elem, int lat,
                                        hipStream_t stream) {
   if (lat == 512 && elem == P_FP16) return launch_latent_prefill<F16, 512>(p, stream);
@@ -775,6 +997,10 @@ template __global__ void mfa_mla_latent_prefill_kernel<F16, 512>(LatentPrefillPa
 template __global__ void mfa_mla_latent_prefill_kernel<BF16, 512>(LatentPrefillParams);
 template __global__ void mfa_mla_latent_prefill_kernel<F16, 256>(LatentPrefillParams);
 template __global__ void mfa_mla_latent_prefill_kernel<BF16, 256>(LatentPrefillParams);
+template __global__ void mfa_mla_latent_paged_rope_kernel<F16, 512>(LatentPagedRopeParams);
+template __global__ void mfa_mla_latent_paged_rope_kernel<BF16, 512>(LatentPagedRopeParams);
+template __global__ void mfa_mla_latent_paged_rope_kernel<F16, 256>(LatentPagedRopeParams);
+template __global__ void mfa_mla_latent_paged_rope_kernel<BF16, 256>(LatentPagedRopeParams);
 template __global__ void mfa_mla_latent_paged_kernel<F16, 512>(LatentPagedParams);
 template __global__ void mfa_mla_latent_paged_kernel<BF16, 512>(LatentPagedParams);
 template __global__ void mfa_mla_latent_paged_kernel<F16, 256>(LatentPagedParams);

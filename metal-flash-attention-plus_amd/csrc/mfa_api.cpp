@@ -2251,6 +2251,38 @@ mfa_status_t paged_latent_buffers(const char* what, const mfa_paged_latent_cache
   return MFA_SUCCESS;
 }
 
+// A checked mfa_paged_rope_cache_t, the second view of the latent cache's pages: the latent
+// pool's stride rules on rows of rope_dim elements (stride index 1 in a message is the token
+// stride).  The pool's type is the descriptor's by contract; the struct has no field to check.
+constexpr int kRopeDim = 64;
+mfa_status_t paged_rope_view(const char* what, const mfa_paged_rope_cache_t& r) {
+  if (r.rope_dim != (uint32_t)kRopeDim)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: rope dimension %u (64)", what, r.rope_dim);
+  for (int i = 0; i < 2; ++i)
+    if (r.strides[i] < 0 || (r.strides[i] * 2) % 16 != 0)
+      return fail(MFA_ERR_UNSUPPORTED, "%s: rope stride %d is not a multiple of 16 bytes", what, i);
+  if (r.strides[1] < kRopeDim || r.strides[1] * 2 >= ((int64_t)1 << 24))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: rope token stride %lld", what, (long long)r.strides[1]);
+  return MFA_SUCCESS;
+}
+
+// The rope struct of a plan query: the given one with a null pool replaced or, without one, a
+// dense pool of its own over the latent cache's pages.
+mfa_paged_rope_cache_t plan_rope(const mfa_paged_rope_cache_t* rope,
+                                 const mfa_paged_latent_cache_t& c) {
+  mfa_paged_rope_cache_t r;
+  if (rope) {
+    r = *rope;
+  } else {
+    memset(&r, 0, sizeof(r));
+    r.rope_dim = kRopeDim;
+    r.strides[1] = kRopeDim;
+    r.strides[0] = (int64_t)c.page_size * kRopeDim;
+  }
+  fill_dummy(r.pool);
+  return r;
+}
+
 // paged_plan for the one-pool cache: without one, a dense 16-bit cache of 256-key pages.
 template <class Desc, class Run>
 mfa_status_t paged_latent_plan(const Desc& d, const mfa_paged_latent_cache_t* cache,
@@ -2279,9 +2311,12 @@ mfa_status_t paged_latent_plan(const Desc& d, const mfa_paged_latent_cache_t* ca
 // descriptor, the cache view, the masks, the scale and the grids.  Decode: the projection's grid
 // z is 32 batch rows per workgroup (R = 1, B > 1) or one (b, h) each; prefill: one (b, h) each
 // for every shape, and its B · ceil(H·R / 32) workgroups follow from B · H · R < 2^31.
+// with_rope (mfa_paged_mla_rope_decode_forward): a given rope struct is checked behind the cache
+// struct (a null one is the buffers' fault, later), and the scale falls back to the joint width.
 mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* desc,
                             const mfa_paged_latent_cache_t* cache, bool prefill,
-                            PagedCacheView* cv, float* scale_out) {
+                            PagedCacheView* cv, float* scale_out, bool with_rope = false,
+                            const mfa_paged_rope_cache_t* rope = nullptr) {
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const mfa_attention_descriptor_t& base = desc->base;
   const int64_t B = desc->batch_size, H = desc->num_heads, R = desc->rows;
@@ -2298,6 +2333,7 @@ mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* 
   mfa_status_t st =
       paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "descriptor's", cv);
   if (st != MFA_SUCCESS) return st;
+  if (with_rope && rope && (st = paged_rope_view(what, *rope)) != MFA_SUCCESS) return st;
   if (D % 8 != 0 || D > 256)
     return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of 8, at most 256)",
                 what, (long long)D);
@@ -2306,7 +2342,7 @@ mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* 
                                base.sparsity_pattern != MFA_SPARSITY_CAUSAL))
     return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal", what);
   if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
-  const float scale = resolve_scale(base, (int)D);
+  const float scale = resolve_scale(base, (int)D + (with_rope ? kRopeDim : 0));
   if (!(scale > 0.f) || !(1.442695041f * scale > 0.f))
     return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
   if (B * H * R >= ((int64_t)1 << 31))
@@ -2323,12 +2359,19 @@ mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* 
 // ... and the buffers of a call that computes something.
 mfa_status_t paged_mla_buffers(const char* what, const mfa_paged_latent_cache_t& cache,
                                const void* query, const void* w_k, const void* w_v,
-                               const void* output) {
-  const mfa_status_t st = paged_latent_buffers(what, cache, "query, w_k, w_v, output",
-                                               query && w_k && w_v && output);
+                               const void* output, bool with_rope = false,
+                               const void* q_rope = nullptr,
+                               const mfa_paged_rope_cache_t* rope = nullptr) {
+  const bool own = query && w_k && w_v && output;
+  const mfa_status_t st =
+      with_rope ? paged_latent_buffers(what, cache, "query, q_rope, w_k, w_v, output, the rope pool",
+                                       own && q_rope && rope && rope->pool)
+                : paged_latent_buffers(what, cache, "query, w_k, w_v, output", own);
   if (st != MFA_SUCCESS) return st;
   if (!aligned16(query) || !aligned16(w_k) || !aligned16(w_v))
     return fail(MFA_ERR_UNSUPPORTED, "%s: query and weights must be 16-byte aligned", what);
+  if (with_rope && (!aligned16(q_rope) || !aligned16(rope->pool)))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: q_rope and the rope pool must be 16-byte aligned", what);
   return MFA_SUCCESS;
 }
 
@@ -2336,21 +2379,28 @@ mfa_status_t paged_mla_buffers(const char* what, const mfa_paged_latent_cache_t&
 // shape), mfa_mla_latent_paged_kernel over absorbed_layout's split at S_kv = cap, and the merge
 // that applies W_v — three launches for any split count.  Q̃ and the partials live in library
 // scratch slot 16, sized by the descriptor alone.
+// with_rope (mfa_paged_mla_rope_decode_forward): the same route and scratch with
+// mfa_mla_latent_paged_rope_kernel in the latent kernel's place — the rope pool as a second view
+// of the cache's pages, q_rope [B, H, R, 64] next to Q̃.
 mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void* query,
                               const void* w_k, const void* w_v,
                               const mfa_paged_latent_cache_t* cache, float* output,
-                              void* logsumexp, hipStream_t stream) {
-  const char* const what = "paged MLA decode";
+                              void* logsumexp, hipStream_t stream, bool with_rope = false,
+                              const void* q_rope = nullptr,
+                              const mfa_paged_rope_cache_t* rope = nullptr) {
+  const char* const what = with_rope ? "paged MLA rope decode" : "paged MLA decode";
   PagedCacheView cv;
   float scale = 0.f;
-  mfa_status_t st = paged_mla_view(what, desc, cache, false, &cv, &scale);
+  mfa_status_t st = paged_mla_view(what, desc, cache, false, &cv, &scale, with_rope, rope);
   if (st != MFA_SUCCESS) return st;
   const mfa_attention_descriptor_t& base = desc->base;
   const int64_t B = desc->batch_size, H = desc->num_heads, R = desc->rows;
   const int64_t D = desc->head_dim, Lat = desc->kv_latent_dim;
   const int prec = desc->precision;
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
-  if ((st = paged_mla_buffers(what, *cache, query, w_k, w_v, output)) != MFA_SUCCESS) return st;
+  if ((st = paged_mla_buffers(what, *cache, query, w_k, w_v, output, with_rope, q_rope, rope)) !=
+      MFA_SUCCESS)
+    return st;
 
   const AbsorbedLayout al = absorbed_layout((int)B, (int)H, (int)R, (int)cv.cap, (int)Lat);
   if ((int64_t)al.nblk * B * al.nsplit >= ((int64_t)1 << 31))
@@ -2385,7 +2435,19 @@ mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void
   p.l.H = (int)H; p.l.D = (int)D;
   p.pg = cv.pg;
   p.tok_bytes = cache->strides[1] * cv.es;
-  const hipError_t e = mfa::mla_latent_paged_dispatch(p, elem_of(prec), (int)Lat, stream);
+  hipError_t e;
+  if (with_rope) {
+    mfa::LatentPagedRopeParams pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.c = p;
+    pr.rope = rope->pool;
+    pr.rope_page_bytes = rope->strides[0] * cv.es;
+    pr.rope_tok_bytes = rope->strides[1] * cv.es;
+    pr.q_rope = q_rope;
+    e = mfa::mla_latent_paged_rope_dispatch(pr, elem_of(prec), (int)Lat, stream);
+  } else {
+    e = mfa::mla_latent_paged_dispatch(p, elem_of(prec), (int)Lat, stream);
+  }
   if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
   return hip_status(e, "paged MLA latent attention launch");
 }
@@ -2449,11 +2511,16 @@ mfa_status_t paged_mla_prefill(const mfa_paged_mla_descriptor_t* desc, const voi
 
 // The write side: paged_append's kernel with one operand — one pool, one "head" of Lat
 // elements, no head stride.
+// with_rope (mfa_paged_latent_rope_append): the rope key rows k_rope [B, R, 64] go with the latent
+// rows, to the same slots of the rope view, in one launch of a kernel with two operand widths.
 mfa_status_t paged_latent_append(const mfa_paged_latent_append_descriptor_t* desc,
                                  const void* latent, const int64_t* latent_strides,
                                  const int32_t* new_lens, const mfa_paged_latent_cache_t* cache,
-                                 hipStream_t stream) {
-  const char* const what = "paged latent append";
+                                 hipStream_t stream, bool with_rope = false,
+                                 const void* k_rope = nullptr,
+                                 const int64_t* k_rope_strides = nullptr,
+                                 const mfa_paged_rope_cache_t* rope = nullptr) {
+  const char* const what = with_rope ? "paged latent rope append" : "paged latent append";
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const int64_t B = desc->batch_size, R = desc->rows, Lat = desc->kv_latent_dim;
   if (Lat == 0 || desc->max_seq_len == 0 || cache->max_pages_per_seq == 0 || cache->num_pages == 0)
@@ -2468,11 +2535,16 @@ mfa_status_t paged_latent_append(const mfa_paged_latent_append_descriptor_t* des
   mfa_status_t st =
       paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "input's", &cv);
   if (st != MFA_SUCCESS) return st;
+  if (with_rope && rope && (st = paged_rope_view(what, *rope)) != MFA_SUCCESS) return st;
   if (B * R >= ((int64_t)1 << 31))
     return fail(MFA_ERR_UNSUPPORTED, "%s: too many rows", what);
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to write; the buffers may be null
-  if ((st = paged_latent_buffers(what, *cache, "latent", latent != nullptr)) != MFA_SUCCESS)
-    return st;
+  st = with_rope ? paged_latent_buffers(what, *cache, "latent, k_rope, the rope pool",
+                                        latent && k_rope && rope && rope->pool)
+                 : paged_latent_buffers(what, *cache, "latent", latent != nullptr);
+  if (st != MFA_SUCCESS) return st;
+  if (with_rope && !aligned16(rope->pool))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: the rope pool must be 16-byte aligned", what);
 
   const int64_t dense[2] = {R * Lat, Lat};
   const int64_t* s = latent_strides ? latent_strides : dense;
@@ -2482,6 +2554,32 @@ mfa_status_t paged_latent_append(const mfa_paged_latent_append_descriptor_t* des
     if (s[j] < 0 || s[j] % 8 != 0)
       return fail(MFA_ERR_UNSUPPORTED, "%s: latent stride %d is not a multiple of 8 elements",
                   what, j);
+  if (with_rope) {
+    const int64_t rdense[2] = {R * kRopeDim, kRopeDim};
+    const int64_t* rs = k_rope_strides ? k_rope_strides : rdense;
+    if (!aligned16(k_rope))
+      return fail(MFA_ERR_UNSUPPORTED, "%s: k_rope rows must be 16-byte aligned", what);
+    for (int j = 0; j < 2; ++j)
+      if (rs[j] < 0 || rs[j] % 8 != 0)
+        return fail(MFA_ERR_UNSUPPORTED, "%s: k_rope stride %d is not a multiple of 8 elements",
+                    what, j);
+    mfa::PagedRopeAppendParams pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.src[0] = latent; pr.src[1] = k_rope;
+    pr.pool[0] = const_cast<void*>(cache->pool); pr.pool[1] = const_cast<void*>(rope->pool);
+    pr.s_sb[0] = s[0] * 2; pr.s_ss[0] = s[1] * 2;
+    pr.s_sb[1] = rs[0] * 2; pr.s_ss[1] = rs[1] * 2;
+    pr.page_bytes[0] = cache->strides[0] * cv.es; pr.tok_bytes[0] = cache->strides[1] * cv.es;
+    pr.page_bytes[1] = rope->strides[0] * cv.es; pr.tok_bytes[1] = rope->strides[1] * cv.es;
+    pr.chunks[0] = (int)Lat / 8; pr.chunks[1] = kRopeDim / 8;
+    pr.pg = cv.pg;
+    pr.new_lens = new_lens;
+    pr.R = (int)R;
+    pr.cap = (int)cv.cap;
+    pr.rows_total = (int)(B * R);
+    return hip_status(mfa::paged_rope_append_dispatch(pr, stream),
+                      "mfa_paged_latent_rope_append launch");
+  }
   mfa::PagedAppendParams p;
   memset(&p, 0, sizeof(p));
   p.src[0] = latent;
@@ -2632,3 +2730,44 @@ extern "C" mfa_status_t mfa_paged_latent_append_plan(
   });
 }
 
+
+extern "C" mfa_status_t mfa_paged_mla_rope_decode_forward(
+    const mfa_paged_mla_descriptor_t* desc, const void* query, const void* q_rope, const void* w_k,
+    const void* w_v, const mfa_paged_latent_cache_t* cache, const mfa_paged_rope_cache_t* rope,
+    float* output, void* logsumexp, void* stream) {
+  return paged_mla_decode(desc, query, w_k, w_v, cache, output, logsumexp, (hipStream_t)stream,
+                          true, q_rope, rope);
+}
+
+extern "C" mfa_status_t mfa_paged_mla_rope_decode_plan(const mfa_paged_mla_descriptor_t* desc,
+                                                       const mfa_paged_latent_cache_t* cache,
+                                                       const mfa_paged_rope_cache_t* rope,
+                                                       mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  const void* const vd = (const void*)kPlanDummy;
+  return paged_latent_plan(*desc, cache, out, [&](const mfa_paged_latent_cache_t& c) {
+    const mfa_paged_rope_cache_t r = plan_rope(rope, c);
+    return paged_mla_decode(desc, vd, vd, vd, &c, (float*)kPlanDummy, nullptr, nullptr, true, vd,
+                            &r);
+  });
+}
+
+extern "C" mfa_status_t mfa_paged_latent_rope_append(
+    const mfa_paged_latent_append_descriptor_t* desc, const void* latent,
+    const int64_t* latent_strides, const void* k_rope, const int64_t* k_rope_strides,
+    const int32_t* new_lens, const mfa_paged_latent_cache_t* cache,
+    const mfa_paged_rope_cache_t* rope, void* stream) {
+  return paged_latent_append(desc, latent, latent_strides, new_lens, cache, (hipStream_t)stream,
+                             true, k_rope, k_rope_strides, rope);
+}
+
+extern "C" mfa_status_t mfa_paged_latent_rope_append_plan(
+    const mfa_paged_latent_append_descriptor_t* desc, const mfa_paged_latent_cache_t* cache,
+    const mfa_paged_rope_cache_t* rope, mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  const void* const vd = (const void*)kPlanDummy;
+  return paged_latent_plan(*desc, cache, out, [&](const mfa_paged_latent_cache_t& c) {
+    const mfa_paged_rope_cache_t r = plan_rope(rope, c);
+    return paged_latent_append(desc, vd, nullptr, nullptr, &c, nullptr, true, vd, nullptr, &r);
+  });
+}

@@ -92,6 +92,9 @@ hipError_t fwd_prefill_paged_kv8_dispatch(const FwdParams& p, const PagedKv& pg,
 // pool of mfa_paged_latent_append, one "head" of kv_latent_dim elements).
 hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8, int operands,
                                  hipStream_t stream);
+// The latent row and its 64-element rope key row to slot t of the same page, one launch
+// (mfa_paged_latent_rope_append); 16-bit rows of either type, the bits unchanged.
+hipError_t paged_rope_append_dispatch(const PagedRopeAppendParams& p, hipStream_t stream);
 // FP16 Q with per-tensor INT8 / INT4 K/V (src SRC_I8 / SRC_I4) widened on load inside the
 // shared-tile loop (attention_fwd_kv8.hip); D <= 128 padded to 128, no masks.
 hipError_t fwd_kv8_dispatch(const FwdParams& p, int elem, int DP, int src, hipStream_t stream);
@@ -123,6 +126,9 @@ hipError_t mla_latent_dispatch(const LatentParams& p, int elem, int lat, hipStre
 // split count (p.l.nsplit >= 1).
 hipError_t mla_latent_paged_dispatch(const LatentPagedParams& p, int elem, int lat,
                                      hipStream_t stream);
+// ... with the rope key part: mfa_mla_latent_paged_rope_kernel, then the same merge.
+hipError_t mla_latent_paged_rope_dispatch(const LatentPagedRopeParams& p, int elem, int lat,
+                                          hipStream_t stream);
 // Ragged prompt chunks over that cache: one launch of 32-row query blocks, no key split, the
 // 16-bit latent-space output in p.c.l.olat (the caller applies W_v).
 hipError_t mla_latent_prefill_dispatch(const LatentPrefillParams& p, int elem, int lat,

@@ -140,6 +140,22 @@ struct PagedAppendParams {
   int32_t rows_total;          // B · R
 };
 
+// Append to a paged latent cache with its rope part (paged_append.hip,
+// mfa_paged_rope_append_kernel): index 0 of each pair is the latent, 1 the rope key row.
+struct PagedRopeAppendParams {
+  const void* src[2];          // new rows [B, R, width], 16-bit, d contiguous
+  void* pool[2];
+  int64_t s_sb[2], s_ss[2];    // BYTE strides of the sources: batch, row
+  int64_t page_bytes[2];       // byte stride between the pages of each pool
+  int64_t tok_bytes[2];        // ... and between the token slots of a page
+  int32_t chunks[2];           // 16-byte chunks per row: width / 8
+  PagedKv pg;                  // table and lengths (after the append); page_bytes is unused
+  const int32_t* new_lens;     // [B] rows to append per sequence (clamped to [0, R]); NULL: R
+  int32_t R;
+  int32_t cap;                 // positions at or past it are dropped
+  int32_t rows_total;          // B · R
+};
+
 // MFMA GEMM (gemm.hip): C = A·B (+C); two (B, C) pairs share A when b[1] != nullptr.
 struct GemmParams {
   const void* a;
@@ -183,6 +199,17 @@ struct LatentPagedParams {
   LatentParams l;
   PagedKv pg;          // one [page][LAT] row set per page: head_bytes is unused
   int64_t tok_bytes;   // byte stride between the token slots of a page
+};
+
+// ... with a decoupled RoPE key part next to the latent (mfa_mla_latent_paged_rope_kernel): a
+// second view of the same pages, slots and block table, 64 elements per key shared by every head,
+// and the rope part of the query.  c.l.c_log2 is the scale of the joint head_dim + 64 product.
+struct LatentPagedRopeParams {
+  LatentPagedParams c;
+  const void* rope;          // the rope pool (or the latent pool + LAT elements: fused rows)
+  int64_t rope_page_bytes;   // byte stride between its pages
+  int64_t rope_tok_bytes;    // ... and between the token slots of a page
+  const void* q_rope;        // [B][R][64] 16-bit, R = H·S_q as in c.l
 };
 
 // Ragged prompt chunks over the same cache (mfa_mla_latent_prefill_kernel): c.l.Sq is the rows

@@ -2,9 +2,9 @@
 // (attention_mla_latent.hip), as text.
 //
 // Not a stand-alone header: it is the statements of one iteration of the key loop, included
-// inside mfa_mla_latent_kernel, mfa_mla_latent_paged_kernel and mfa_mla_latent_prefill_kernel,
-// between the staging of the next tile's loads and their store to LDS.  The three kernels differ
-// in how a tile reaches LDS and in what leaves the loop; the arithmetic on a staged tile, and its
+// inside mfa_mla_latent_kernel, mfa_mla_latent_paged_kernel, mfa_mla_latent_prefill_kernel and
+// mfa_mla_latent_paged_rope_kernel, between the staging of the next tile's loads and their store to LDS.  The three kernels differ
+// in how a tile reaches LDS and in what leaves the loop (the rope kernel also in one more k-step); the arithmetic on a staged tile, and its
 // order, is this text alone, which is what makes their results comparable bit for bit.
 // Contract of the place that includes it:
 //   * a __global__ function template with parameters E and LAT, the constants BK, DS, ND, WS,
@@ -14,12 +14,21 @@
 //   * the running state `m`, `lh`, `o[ND]`, which it updates;
 //   * MLA_TILE_LEN, the key count of the sequence (keys at or past it are −inf), and
 //     MLA_TILE_KLIM, the last key the lane's row sees when p.causal (later keys take the finite
-//     mask value), defined by the includer and undefined here.
+//     mask value), defined by the includer and undefined here;
+//   * optionally MLA_TILE_ROPE_FETCH(), which only the rope kernel defines: the tile then has a
+//     rope k-step — `krf`, this tile's key rope fragment (row l32, elements 16·wave + 8·hh), times
+//     `qrf`, the row's q_rope fragment, into the partial Sᵀ before the exchange — and the macro's
+//     statement, which requests the next tile's `krf`, runs after the exchange sum.  Without the
+//     macro the text below is what it was before the macro existed.
 // Why text and not a function: see decode16_quant_body.h — the latent kernels sit at 249 VGPRs
 // at latent 512, and the statements included in place compile to the code they compiled to
 // when each kernel held its own copy.
     // Partial S^T over this wave's latent slice.
+#ifdef MLA_TILE_ROPE_SP
+    f32x16 sp = MLA_TILE_ROPE_SP;
+#else
     f32x16 sp = zero16();
+#endif
 #pragma unroll
     for (int ds = 0; ds < DS; ++ds)
       sp = A::mma(A::read_row(kt, l32, wave * DS + ds, hh), qf[ds], sp);
@@ -49,6 +58,10 @@
         for (int e = 0; e < 4; ++e)
           s[4 * q + e] = ((part[0][q][e] + part[1][q][e]) + part[2][q][e]) + part[3][q][e];
     }
+#ifdef MLA_TILE_ROPE_SP
+    // `part` is dead: the next tile's rope fragment takes four of its registers.
+    MLA_TILE_ROPE_FETCH();
+#endif
 
     if (t + BK > MLA_TILE_LEN || (p.causal && t + BK - 1 > MLA_TILE_KLIM)) {
       MFA_KEEP_BRANCH();
@@ -97,3 +110,7 @@
     }
 #undef MLA_TILE_LEN
 #undef MLA_TILE_KLIM
+#ifdef MLA_TILE_ROPE_SP
+#undef MLA_TILE_ROPE_SP
+#undef MLA_TILE_ROPE_FETCH
+#endif

@@ -11,6 +11,9 @@
 // mfa_paged_latent_append is the same kernel with one operand (grid.y = 1): the MLA latent pool
 // as a key pool with one "head" of kv_latent_dim elements and no head stride.
 //
+// mfa_paged_latent_rope_append has a kernel of its own below: two operands of different widths
+// (the latent row and its 64-element rope key row) into two views of the same pages.
+//
 // Memory-bound, one launch for K and V (blockIdx.y picks the operand).  A wave owns one
 // (sequence, row) at a time: length, row count and block-table entry are uniform loads on the
 // scalar path and the position, page and both base addresses are formed once per row; the lanes
@@ -113,6 +116,46 @@ __global__ __launch_bounds__(64 * kAppendWaves) void mfa_paged_append_kernel(Pag
       }
     }
   }
+}
+
+// The latent row and its rope key row of one new token, to slot t of the same page in two views
+// of it (one fused [latent | rope] row, or two pools): mfa_paged_append_kernel's addressing — a
+// wave per (sequence, row), position and page formed once from uniform loads — with the lanes
+// walking the latent's 16-byte chunks and then the rope row's, each under its own strides.  16-bit
+// rows of either type: the bits are copied, so the kernel has no element parameter.
+__global__ __launch_bounds__(64 * kAppendWaves) void mfa_paged_rope_append_kernel(
+    PagedRopeAppendParams p) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int nlat = p.chunks[0], nall = p.chunks[0] + p.chunks[1];
+  for (int64_t row64 = (int64_t)blockIdx.x * kAppendWaves + wave; row64 < p.rows_total;
+       row64 += (int64_t)gridDim.x * kAppendWaves) {
+    const int row = (int)row64;
+    const int b = row / p.R, r = row - b * p.R;
+    const int len = ((append_i32_ptr)p.pg.seq_lens)[b];
+    const int n = p.new_lens ? min(max(((append_i32_ptr)p.new_lens)[b], 0), p.R) : p.R;
+    const int64_t t64 = (int64_t)len - n + r;  // any int32 length: no wrap
+    if (r >= n || t64 < 0 || t64 >= p.cap) continue;
+    const int t = (int)t64;  // < cap <= max_pages * page: the lookup stays in the table row
+    const int entry = ((append_i32_ptr)p.pg.block_table)[(int64_t)b * p.pg.max_pages +
+                                                         (t >> p.pg.lg_page)];
+    const int page = min(max(entry, 0), p.pg.num_pages - 1);
+    const int slot = t & ((1 << p.pg.lg_page) - 1);
+    for (int c = lane; c < nall; c += 64) {
+      const int w = c >= nlat, ch = c - (w ? nlat : 0);   // operand and its chunk
+      const char* const sp = (const char*)p.src[w] + b * p.s_sb[w] + r * p.s_ss[w] + 16 * ch;
+      char* const dp = (char*)p.pool[w] + (int64_t)page * p.page_bytes[w] +
+                       (int64_t)slot * p.tok_bytes[w] + 16 * ch;
+      *(u32x4*)dp = *(const u32x4*)sp;
+    }
+  }
+}
+
+hipError_t paged_rope_append_dispatch(const PagedRopeAppendParams& p, hipStream_t stream) {
+  // mfa_paged_append_kernel's grid for one operand.
+  const int64_t wgs = (p.rows_total + kAppendWaves - 1) / kAppendWaves;
+  return launch(mfa_paged_rope_append_kernel, dim3((unsigned)std::min<int64_t>(wgs, 32768)),
+                dim3(64 * kAppendWaves), 0, stream, p);
 }
 
 hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8, int operands,

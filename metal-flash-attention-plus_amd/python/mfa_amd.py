@@ -507,6 +507,30 @@ class PagedLatentCache(ctypes.Structure):
         return c
 
 
+class PagedRopeCache(ctypes.Structure):
+    """mfa_paged_rope_cache_t: the RoPE'd key part of an MLA cache, 64 elements per key shared by
+    every head — a second view of a PagedLatentCache's pages."""
+    _fields_ = [
+        ("pool", ctypes.c_void_p),
+        ("strides", ctypes.c_int64 * 2),
+        ("rope_dim", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, page_size, pool=None, strides=None, rope_dim=64):
+        """Pool [num_pages, page_size, rope_dim] unless `strides` (page, token slot; elements) says
+        otherwise.  Fused [latent | rope] rows: pool = the row tensor's [..., latent:] view and
+        strides = the latent cache's.  The tensor may be None for a plan query."""
+        c = cls()
+        c.pool = _ptr(pool)
+        if strides is None:
+            strides = (page_size * rope_dim, rope_dim)
+        c.strides = (ctypes.c_int64 * 2)(*[int(x) for x in strides])
+        c.rope_dim = rope_dim
+        c._keep = (pool,)  # the struct holds a raw device pointer
+        return c
+
+
 class PagedMLADecodeDescriptor(ctypes.Structure):
     """mfa_paged_mla_descriptor_t: R query rows per head over a paged latent cache."""
     _fields_ = [
@@ -625,6 +649,16 @@ _sig("mfa_paged_latent_append", ctypes.c_int,
      [_P(PagedLatentAppendDescriptor), _V, _P(ctypes.c_int64), _V, _P(PagedLatentCache), _V])
 _sig("mfa_paged_latent_append_plan", ctypes.c_int,
      [_P(PagedLatentAppendDescriptor), _P(PagedLatentCache), _P(KernelPlan)])
+_sig("mfa_paged_mla_rope_decode_forward", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _V, _V, _V, _V, _P(PagedLatentCache), _P(PagedRopeCache), _V,
+      _V, _V])
+_sig("mfa_paged_mla_rope_decode_plan", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _P(PagedLatentCache), _P(PagedRopeCache), _P(KernelPlan)])
+_sig("mfa_paged_latent_rope_append", ctypes.c_int,
+     [_P(PagedLatentAppendDescriptor), _V, _P(ctypes.c_int64), _V, _P(ctypes.c_int64), _V,
+      _P(PagedLatentCache), _P(PagedRopeCache), _V])
+_sig("mfa_paged_latent_rope_append_plan", ctypes.c_int,
+     [_P(PagedLatentAppendDescriptor), _P(PagedLatentCache), _P(PagedRopeCache), _P(KernelPlan)])
 _sig("mfa_quantize_workspace_size", ctypes.c_size_t,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32])
 _sig("mfa_quantize", ctypes.c_int,
@@ -1004,6 +1038,60 @@ def paged_latent_append_plan(desc: PagedLatentAppendDescriptor,
     """mfa_paged_latent_append_plan: the kernel paged_latent_append launches (see
     multihead_plan); without a cache, one of 256-key pages.  Needs no GPU."""
     return _paged_plan(lib.mfa_paged_latent_append_plan, desc, cache)
+
+
+def _rope_plan(fn, desc, cache, rope) -> list[dict]:
+    plan = KernelPlan()
+    check(fn(ctypes.byref(desc), ctypes.byref(cache) if cache is not None else None,
+             ctypes.byref(rope) if rope is not None else None, ctypes.byref(plan)))
+    return plan.as_list()
+
+
+def _strides2(t, strides):
+    if strides is None and hasattr(t, "stride"):
+        strides = t.stride()[:2]
+    return None if strides is None else (ctypes.c_int64 * 2)(*[int(x) for x in strides])
+
+
+def paged_mla_rope_decode_forward(desc: PagedMLADecodeDescriptor, query, q_rope, w_k, w_v,
+                                  cache: PagedLatentCache, rope: PagedRopeCache, output,
+                                  logsumexp=None, stream=None):
+    """mfa_paged_mla_rope_decode_forward: paged_mla_decode_forward with a decoupled RoPE key part
+    next to the latent — scores scale * (query W_k^T latent + q_rope k_rope), values from the
+    latent alone.  q_rope [B, H, R, 64] 16-bit, already rotated; rope: the cache's rope view.  The
+    default scale is 1 / sqrt(head_dim + 64)."""
+    check(lib.mfa_paged_mla_rope_decode_forward(
+        ctypes.byref(desc), _ptr(query), _ptr(q_rope), _ptr(w_k), _ptr(w_v), ctypes.byref(cache),
+        ctypes.byref(rope), _ptr(output), _ptr(logsumexp), _stream(stream)))
+
+
+def paged_mla_rope_decode_plan(desc: PagedMLADecodeDescriptor,
+                               cache: Optional[PagedLatentCache] = None,
+                               rope: Optional[PagedRopeCache] = None) -> list[dict]:
+    """mfa_paged_mla_rope_decode_plan: the kernels paged_mla_rope_decode_forward launches (see
+    multihead_plan); without a rope view, a dense rope pool over the cache's pages.  Needs no
+    GPU."""
+    return _rope_plan(lib.mfa_paged_mla_rope_decode_plan, desc, cache, rope)
+
+
+def paged_latent_rope_append(desc: PagedLatentAppendDescriptor, latent, k_rope,
+                             cache: PagedLatentCache, rope: PagedRopeCache, new_lens=None,
+                             latent_strides=None, k_rope_strides=None, stream=None):
+    """mfa_paged_latent_rope_append: paged_latent_append for both parts of the new tokens — latent
+    [B, R, latent] and k_rope [B, R, 64] go to the same slots of the cache and its rope view in one
+    launch.  Strides (batch, row) default to the tensors' own."""
+    check(lib.mfa_paged_latent_rope_append(
+        ctypes.byref(desc), _ptr(latent), _strides2(latent, latent_strides), _ptr(k_rope),
+        _strides2(k_rope, k_rope_strides), _ptr(new_lens), ctypes.byref(cache), ctypes.byref(rope),
+        _stream(stream)))
+
+
+def paged_latent_rope_append_plan(desc: PagedLatentAppendDescriptor,
+                                  cache: Optional[PagedLatentCache] = None,
+                                  rope: Optional[PagedRopeCache] = None) -> list[dict]:
+    """mfa_paged_latent_rope_append_plan: the kernel paged_latent_rope_append launches.  Needs no
+    GPU."""
+    return _rope_plan(lib.mfa_paged_latent_rope_append_plan, desc, cache, rope)
 
 
 def quantize(x, target: Precision, mode: QuantMode = QuantMode.tensorWise, rows=None, cols=None,
