@@ -888,8 +888,8 @@ typedef struct mfa_paged_rope_cache {
  * MFMA k-step per wave for the rope dimensions (the rope rows go from global memory straight into
  * the operand registers, a tile ahead), and the unchanged merge that applies W_v.  With a zero
  * q_rope the result is mfa_paged_mla_decode_forward's bit for bit at the same scale.
- * Out of scope: applying the rotation; a prefill call with a rope part; the dense
- * mfa_mla_forward_absorbed; rope widths other than 64; quantised pools. */
+ * Out of scope: applying the rotation; the dense mfa_mla_forward_absorbed; rope widths other
+ * than 64; quantised pools.  Prompts go through mfa_paged_mla_rope_prefill_forward. */
 mfa_status_t mfa_paged_mla_rope_decode_forward(const mfa_paged_mla_descriptor_t* desc,
                                                const void* query, const void* q_rope,
                                                const void* w_k, const void* w_v,
@@ -921,6 +921,44 @@ mfa_status_t mfa_paged_latent_rope_append_plan(const mfa_paged_latent_append_des
                                                const mfa_paged_latent_cache_t* cache,
                                                const mfa_paged_rope_cache_t* rope,
                                                mfa_kernel_plan_t* out);
+
+/* mfa_paged_mla_prefill_forward with the rope part: the prompt side of a [latent | rope] cache,
+ * between mfa_paged_latent_rope_append and mfa_paged_mla_rope_decode_forward on one pair of cache
+ * structs.  q_rope: dense [B, H, R, 64] in `precision`, already rotated by the caller; like
+ * `query`, the contents of its rows q >= n_b are never used and may hold NaN or Inf.  Same result
+ * as attention with K_h = [latent * W_k,h | k_rope], Q_h = [query | q_rope], V_h = latent * W_v,h,
+ * up to the 16-bit rounding of Q * W_k^T and of the latent-space output.  The softmax scale is
+ * the base descriptor's, or 1 / sqrt(head_dim + rope_dim).
+ * Everything else is mfa_paged_mla_prefill_forward's contract: lengths AFTER the append, n_b from
+ * new_lens, t_q = len_b - n_b + q, both masks (windows and sparse masks: MFA_ERR_UNSUPPORTED),
+ * dead rows with exact zeros and L at its floor, every output row written and never with NaN, the
+ * clamps, the two limits (B * H < 65536, B * ceil(H * R / 32) < 2^31), the empty call, the scratch
+ * slot and the stream / graph behaviour — seq_lens += n, mfa_paged_latent_rope_append and this
+ * call replay as one graph after one warm-up call.  A rope row is fetched under the latent row's
+ * safety rules: none at or past len_b, none from a page the table does not name for the keys
+ * read.  The structs are checked as in mfa_paged_mla_rope_decode_forward, in that order: NULL
+ * q_rope, rope or rope->pool is MFA_ERR_INVALID_ARGUMENT where the other buffers are checked,
+ * ahead of any alignment fault.
+ * Three launches for any shape, as the no-rope call: Q * W_k^T by the batched general GEMM, the
+ * latent-space attention of 32-row query blocks with one more MFMA k-step per wave for the rope
+ * dimensions (rope rows from global memory straight into the operand registers, a tile ahead),
+ * and the batched general GEMM with W_v.  With a zero q_rope the result is
+ * mfa_paged_mla_prefill_forward's bit for bit at the same scale.
+ * This call does not split the keys: a short chunk over a very long prefix (few rows, many keys)
+ * remains mfa_paged_mla_rope_decode_forward's shape.  Out of scope: applying the rotation; the
+ * decompress-then-attend route; rope widths other than 64; quantised pools. */
+mfa_status_t mfa_paged_mla_rope_prefill_forward(const mfa_paged_mla_descriptor_t* desc,
+                                                const void* query, const void* q_rope,
+                                                const void* w_k, const void* w_v,
+                                                const int32_t* new_lens,
+                                                const mfa_paged_latent_cache_t* cache,
+                                                const mfa_paged_rope_cache_t* rope,
+                                                float* output, void* logsumexp, void* stream);
+/* The kernels that call launches (see mfa_paged_mla_rope_decode_plan for NULL structs). */
+mfa_status_t mfa_paged_mla_rope_prefill_plan(const mfa_paged_mla_descriptor_t* desc,
+                                             const mfa_paged_latent_cache_t* cache,
+                                             const mfa_paged_rope_cache_t* rope,
+                                             mfa_kernel_plan_t* out);
 
 /* GPU runtime quantization (GEMMQuantization.swift:305-623 semantics, bit-exact; the
  * reference does this on the CPU in QuantizedTensor.from, :720-860).

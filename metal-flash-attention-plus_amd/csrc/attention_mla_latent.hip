@@ -691,6 +691,222 @@ __global__ void __launch_bounds__(256, 2) mfa_mla_latent_prefill_kernel(LatentPr
   }
 }
 
+// The prefill kernel with the decoupled RoPE key part (mfa_paged_mla_rope_prefill_forward):
+// s(q, j) = Q̃_q·c_j + q_pe_q·k_pe_j over ragged prompt chunks.  The work split, the tile
+// staging through LDS, the rows' liveness and the non-split epilogue are the prefill kernel's;
+// the rope k-step is the paged rope kernel's (wave w owns rope dims [16w, 16w + 16), `krf` from
+// global memory straight into the operand registers through the tile's range-checked rope
+// descriptor, requested a tile ahead after the exchange sum, no LDS byte).  What is this
+// kernel's own:
+//   * live and dead rows are interleaved inside a block, and the q_rope row of a dead one may
+//     hold NaN.  The resident `qrf` comes through a descriptor over the block's rows below H·R,
+//     and a dead lane's offset lies outside every such descriptor: its load returns zeros
+//     without a fetch, as its Q̃ fragments are zeros without a load.  No select and no register
+//     is spent on it, and with the zero the rope k-step adds exact zeros to a dead row's
+//     scores, which the epilogue discards anyway;
+//   * the staging loads carry the row step of chunk i in the chunk's descriptor and share one
+//     lane offset (the rope decode kernel's form), which pays for `qrf` and `krf` at latent
+//     512;
+//   * a block with no live row has no key: it loads neither latent, rope nor q_rope bytes.
+template <class E, int LAT>
+__global__ void __launch_bounds__(256, 2)
+    mfa_mla_latent_prefill_rope_kernel(LatentPrefillRopeParams pr) {
+  constexpr int BK = 32, NT = 256;
+  constexpr int WS = LAT / 4;              // latent dims per wave
+  constexpr int DS = WS / 16;              // MFMA k-steps of the wave's QK^T slice
+  constexpr int ND = WS / 32;              // O^T tiles per wave
+  constexpr int CPR = LAT / 8;             // 16-byte chunks per latent row
+  constexpr int CPT = BK * CPR / NT;       // chunks staged per thread
+  constexpr int TILEB = BK * LAT * 2;
+  constexpr int XST = 16;                  // floats per lane in the exchange area
+  constexpr int ROPE = 64;                 // rope elements per key, 16 per wave
+  constexpr int DEAD_OFF = 1 << 30;        // past the end of every q_rope descriptor (<= 4 KiB)
+  using A = Arith16<E, LAT>;
+  using TT = Tile16<LAT>;
+  const LatentPrefillParams& pp = pr.c;
+  const LatentParams& p = pp.c.l;
+  const PagedKv& pg = pp.c.pg;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const tb0 = smem;                              // 2 latent tiles
+  float* const xb = reinterpret_cast<float*>(smem + 2 * TILEB);  // [4 waves][64 lanes][XST]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l32 = lane & 31, hh = lane >> 5;
+  const int b = blockIdx.x / p.nblk;
+  const int r0 = (blockIdx.x % p.nblk) * 32;
+  const int r = r0 + l32;
+  const bool rvalid = r < p.R;
+
+  // The sequence's keys and rows (uniform), and the last key this row sees (-1: a dead row).
+  const int len = min(max(((latent_i32_ptr)pg.seq_lens)[b], 0), p.Skv);
+  const int nrow = pp.new_lens ? min(max(((latent_i32_ptr)pp.new_lens)[b], 0), p.Sq) : p.Sq;
+  const int first = len - nrow;             // key position of the head's row 0
+  int klim = -1;
+  {
+    const int spos = r % p.Sq;              // the row's index among its head's Sq rows
+    if (rvalid && spos < nrow && first + spos >= 0) klim = p.causal ? first + spos : len - 1;
+  }
+
+  // Keys this block needs: none without a live row (every wave holds the same 32 rows, so the
+  // vote is the workgroup's); else all of the sequence, or up to its live rows' largest limit.
+  int kend = 0;
+  if (__builtin_amdgcn_ballot_w64(klim >= 0) != 0) {
+    kend = len;
+    if (p.causal) {
+      const int rl = min(r0 + 31, p.R - 1);
+      const int smax = (r0 / p.Sq == rl / p.Sq) ? min(rl % p.Sq, nrow - 1) : nrow - 1;
+      kend = min(kend, first + smax + 1);
+    }
+  }
+
+  // Q̃ fragments of the wave's slice: d = w·WS + 16·ds + 8·hh + j.
+  i16x8 qf[DS];
+  {
+    const uint16_t* qrow = (const uint16_t*)p.q + ((int64_t)b * p.R + (rvalid ? r : 0)) * LAT;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) {
+      i16x8 v = i16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (klim >= 0) v = *reinterpret_cast<const i16x8*>(qrow + wave * WS + 16 * ds + 8 * hh);
+      qf[ds] = v;
+    }
+  }
+  // The q_rope fragment: d = 16·w + 8·hh + j of row r of the dense [B][R][64] rope query, through
+  // a buffer over the block's rows below R.  A dead lane asks past its end and gets zeros.
+  const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)((const char*)pr.q_rope + ((int64_t)b * p.R + r0) * (ROPE * 2)), (short)0,
+      min(32, p.R - r0) * (ROPE * 2), 0x00020000);
+  auto qrope_load = [&]() {
+    const int off = klim >= 0 ? l32 * (ROPE * 2) + 32 * wave + 16 * hh : DEAD_OFF;
+    return __builtin_bit_cast(i16x8, __builtin_amdgcn_raw_buffer_load_b128(qrs, off, 0, 0));
+  };
+
+  // Block-table entry of the tile at key t (uniform), as stored; the lookup stays in the
+  // sequence's table row (the look-ahead runs past the last tile).
+  const latent_i32_ptr trow = (latent_i32_ptr)pg.block_table + (int64_t)b * pg.max_pages;
+  auto entry = [&](int t) { return trow[min(t >> pg.lg_page, pg.max_pages - 1)]; };
+  const int pmask = (1 << pg.lg_page) - 1;
+  // A tile is one buffer over its page rows below len_b (up to the last such row's end): a
+  // 16-byte load of a row at or past len_b lies outside it and returns zeros without a fetch.
+  // The token strides are below 2^24 bytes, so a tile's row offsets fit the 32-bit buffer offset.
+  const int tokb = (int)pp.c.tok_bytes;
+  const int voff0 = (tid / CPR) * tokb + 16 * (tid % CPR);   // chunk i: row tid / CPR + i·NT / CPR
+  const int vstep = (NT / CPR) * tokb;
+  const int rtokb = (int)pr.rope_tok_bytes;
+  const int roff = l32 * rtokb + 32 * wave + 16 * hh;        // key row l32, elements 16w + 8hh
+  uint4 stg[CPT];
+  // The rope rows of the tile at key t in page entry `ent`: the same page and slots under the
+  // rope strides, the same row count.
+  auto rope_rsrc = [&](int t, int ent, bool wanted) {
+    const int page = min(max(ent, 0), pg.num_pages - 1);
+    const char* const base = (const char*)pr.rope + (int64_t)page * pr.rope_page_bytes +
+                             (int64_t)(t & pmask) * pr.rope_tok_bytes;
+    const int rows = wanted ? min(len - t, BK) : 0;   // 0: an empty buffer, nothing is fetched
+    const int nb = rows > 0 ? (rows - 1) * rtokb + ROPE * 2 : 0;
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, nb, 0x00020000);
+  };
+  auto rope_load = [&](__amdgpu_buffer_rsrc_t rs) {
+    return __builtin_bit_cast(i16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, roff, 0, 0));
+  };
+  auto load = [&](int t, int ent) {
+    const int page = min(max(ent, 0), pg.num_pages - 1);
+    const char* const base = (const char*)p.lat + (int64_t)page * pg.page_bytes +
+                             (int64_t)(t & pmask) * pp.c.tok_bytes;
+    const int nb = (min(len - t, BK) - 1) * tokb + LAT * 2;
+    // Chunk i's rows lie i·NT / CPR rows further on: the step goes into the descriptor (scalar
+    // registers, free after the load issues), not into a lane offset of its own.
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)(base + i * vstep), (short)0, max(nb - i * vstep, 0), 0x00020000);
+      stg[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff0, 0, 0));
+    }
+  };
+  auto store = [&](char* tile) {
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int id = tid + NT * i;
+      *reinterpret_cast<uint4*>(tile + TT::off(id / CPR, id % CPR)) = stg[i];
+    }
+  };
+
+  f32x16 o[ND];
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt) o[dt] = zero16();
+  float m = -kFltMax, lh = 0.f;
+  const float c = p.c_log2;
+
+  int ent_next = 0;
+  // The rope operands of the tile about to be computed.
+  i16x8 krf = i16x8{0, 0, 0, 0, 0, 0, 0, 0}, qrf = krf;
+  if (0 < kend) {
+    const int ent = entry(0);
+    load(0, ent);
+    krf = rope_load(rope_rsrc(0, ent, true));
+    qrf = qrope_load();
+    store(tb0);
+    ent_next = entry(BK);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < kend; t += BK) {
+    const bool has_next = t + BK < kend;
+    // The rope k-step opens the tile's partial Sᵀ, ahead of the next tile's staging loads: its
+    // wait is for the one fragment requested a tile ago, not for the loads issued below.
+    const f32x16 sp_rope = A::mma(krf, qrf, zero16());
+    if (has_next) load(t + BK, ent_next);
+    // Scalar work only; without a next tile the buffer is empty and the request below a no-op.
+    const __amdgpu_buffer_rsrc_t rrs_next = rope_rsrc(t + BK, ent_next, has_next);
+    ent_next = entry(t + 2 * BK);
+    const char* kt = tb0 + cur * TILEB;
+
+#define MLA_TILE_LEN len
+#define MLA_TILE_KLIM klim
+#define MLA_TILE_ROPE_SP sp_rope
+#define MLA_TILE_ROPE_FETCH()              \
+  asm volatile("" : "+v"(s) : : "memory"); \
+  krf = rope_load(rrs_next)
+#include "mla_latent_tile_body.h"
+    if (has_next) store(tb0 + (cur ^ 1) * TILEB);
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  float l = cross_half_sum(lh) + kFltMin;
+  if (!(l > 0.f)) l = kFltMin;
+  if (!rvalid) return;
+  const bool live = klim >= 0;
+  const float inv = 1.f / l;
+  uint16_t* orow = (uint16_t*)p.olat + ((int64_t)b * p.R + r) * LAT + wave * WS;
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d = dt * 32 + 8 * g + 4 * hh;
+      // The product rounded to FP32 and then to E, as in the prefill kernel (see there).
+      float x[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x[e] = o[dt][4 * g + e] * inv;
+        asm("" : "+v"(x[e]));
+      }
+      ushort4 v;
+      v.x = E::from_f32(x[0]);
+      v.y = E::from_f32(x[1]);
+      v.z = E::from_f32(x[2]);
+      v.w = E::from_f32(x[3]);
+      if (!live) v = make_ushort4(0, 0, 0, 0);
+      *reinterpret_cast<ushort4*>(orow + d) = v;
+    }
+  if (wave == 0 && hh == 0 && p.l) {
+    const float L = live ? m + __log2f(l) : -kFltMax;
+    const int64_t li = (int64_t)b * p.R + r;
+    if (p.l_f16)
+      reinterpret_cast<uint16_t*>(p.l)[li] = f32_to_f16(L);
+    else
+      reinterpret_cast<float*>(p.l)[li] = L;
+  }
+}
+
 // Merge of the key splits (flash-decoding): M = max m_s, w_s = exp2(m_s − M),
 // Õ = Σ w_s Õ_s / Σ w_s l_s, L = M + log2 Σ w_s l_s.  MNB rows (the same query row r of MNB
 // consecutive batch items) per 256-thread workgroup, launched with MNB = 1.  The split states
@@ -877,6 +1093,17 @@ static hipError_t launch_latent_prefill(const LatentPrefillParams& p, hipStream_
                 p);
 }
 
+// The paged prefill with the rope key part: the same single launch with the rope kernel.
+template <class E, int LAT>
+static hipError_t launch_latent_prefill_rope(const LatentPrefillRopeParams& p, hipStream_t stream) {
+  constexpr int LDS = 2 * 32 * LAT * 2 + 4 * 64 * 16 * 4;
+  const LatentParams& l = p.c.c.l;
+  if (!l.q || !l.olat || l.Sq < 1 || l.nblk < 1 || !p.rope || !p.q_rope)
+    return hipErrorInvalidValue;
+  return launch(mfa_mla_latent_prefill_rope_kernel<E, LAT>, dim3(l.nblk * l.B), dim3(256), LDS,
+                stream, p);
+}
+
 // Decode query projection Q̃[b, h, :] = q[b, h, :] · W_k[:, h·D : (h+1)·D]ᵀ (S_q = 1): a workgroup
 // takes one head, QC latent columns and 32 batch rows; the W_k slice [QC][D] and the query rows
 // [32][D] sit in LDS (rows padded by 16 B), each thread accumulates QC/8 columns of one row in
@@ -993,6 +1220,19 @@ hipError_t mla_latent_prefill_dispatch(const LatentPrefillParams& p, int elem, i
   return hipErrorNotSupported;
 }
 
+hipError_t mla_latent_prefill_rope_dispatch(const LatentPrefillRopeParams& p, int elem, int lat,
+                                            hipStream_t stream) {
+  if (lat == 512 && elem == P_FP16) return launch_latent_prefill_rope<F16, 512>(p, stream);
+  if (lat == 512 && elem == P_BF16) return launch_latent_prefill_rope<BF16, 512>(p, stream);
+  if (lat == 256 && elem == P_FP16) return launch_latent_prefill_rope<F16, 256>(p, stream);
+  if (lat == 256 && elem == P_BF16) return launch_latent_prefill_rope<BF16, 256>(p, stream);
+  return hipErrorNotSupported;
+}
+
+template __global__ void mfa_mla_latent_prefill_rope_kernel<F16, 512>(LatentPrefillRopeParams);
+template __global__ void mfa_mla_latent_prefill_rope_kernel<BF16, 512>(LatentPrefillRopeParams);
+template __global__ void mfa_mla_latent_prefill_rope_kernel<F16, 256>(LatentPrefillRopeParams);
+template __global__ void mfa_mla_latent_prefill_rope_kernel<BF16, 256>(LatentPrefillRopeParams);
 template __global__ void mfa_mla_latent_prefill_kernel<F16, 512>(LatentPrefillParams);
 template __global__ void mfa_mla_latent_prefill_kernel<BF16, 512>(LatentPrefillParams);
 template __global__ void mfa_mla_latent_prefill_kernel<F16, 256>(LatentPrefillParams);

@@ -2311,8 +2311,9 @@ mfa_status_t paged_latent_plan(const Desc& d, const mfa_paged_latent_cache_t* ca
 // descriptor, the cache view, the masks, the scale and the grids.  Decode: the projection's grid
 // z is 32 batch rows per workgroup (R = 1, B > 1) or one (b, h) each; prefill: one (b, h) each
 // for every shape, and its B · ceil(H·R / 32) workgroups follow from B · H · R < 2^31.
-// with_rope (mfa_paged_mla_rope_decode_forward): a given rope struct is checked behind the cache
-// struct (a null one is the buffers' fault, later), and the scale falls back to the joint width.
+// with_rope (the two rope calls, decode and prefill): a given rope struct is checked behind the
+// cache struct (a null one is the buffers' fault, later), and the scale falls back to the joint
+// width.
 mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* desc,
                             const mfa_paged_latent_cache_t* cache, bool prefill,
                             PagedCacheView* cv, float* scale_out, bool with_rope = false,
@@ -2459,21 +2460,28 @@ mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void
 // batched general GEMM into the FP32 output (a dead row's zero Õ gives an exact-zero O row).
 // Q̃ and Õ, 16-bit [B, H·R, Lat] each, live in library scratch slot 17, sized by the descriptor
 // alone.
+// with_rope (mfa_paged_mla_rope_prefill_forward): the same route and scratch with
+// mfa_mla_latent_prefill_rope_kernel in the middle — the rope pool as a second view of the
+// cache's pages, q_rope [B, H, R, 64] next to Q̃, the rope decode call's rules and scale.
 mfa_status_t paged_mla_prefill(const mfa_paged_mla_descriptor_t* desc, const void* query,
                                const void* w_k, const void* w_v, const int32_t* new_lens,
                                const mfa_paged_latent_cache_t* cache, float* output,
-                               void* logsumexp, hipStream_t stream) {
-  const char* const what = "paged MLA prefill";
+                               void* logsumexp, hipStream_t stream, bool with_rope = false,
+                               const void* q_rope = nullptr,
+                               const mfa_paged_rope_cache_t* rope = nullptr) {
+  const char* const what = with_rope ? "paged MLA rope prefill" : "paged MLA prefill";
   PagedCacheView cv;
   float scale = 0.f;
-  mfa_status_t st = paged_mla_view(what, desc, cache, true, &cv, &scale);
+  mfa_status_t st = paged_mla_view(what, desc, cache, true, &cv, &scale, with_rope, rope);
   if (st != MFA_SUCCESS) return st;
   const mfa_attention_descriptor_t& base = desc->base;
   const int B = (int)desc->batch_size, H = (int)desc->num_heads, R = (int)desc->rows;
   const int D = (int)desc->head_dim, Lat = (int)desc->kv_latent_dim;
   const int prec = desc->precision;
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
-  if ((st = paged_mla_buffers(what, *cache, query, w_k, w_v, output)) != MFA_SUCCESS) return st;
+  if ((st = paged_mla_buffers(what, *cache, query, w_k, w_v, output, with_rope, q_rope, rope)) !=
+      MFA_SUCCESS)
+    return st;
 
   const size_t qbytes = ((size_t)B * H * R * Lat * 2 + 255) & ~(size_t)255;
   void* ws = (void*)kPlanDummy;
@@ -2501,7 +2509,19 @@ mfa_status_t paged_mla_prefill(const mfa_paged_mla_descriptor_t* desc, const voi
   p.c.pg = cv.pg;
   p.c.tok_bytes = cache->strides[1] * cv.es;
   p.new_lens = new_lens;
-  const hipError_t e = mfa::mla_latent_prefill_dispatch(p, elem_of(prec), Lat, stream);
+  hipError_t e;
+  if (with_rope) {
+    mfa::LatentPrefillRopeParams pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.c = p;
+    pr.rope = rope->pool;
+    pr.rope_page_bytes = rope->strides[0] * cv.es;
+    pr.rope_tok_bytes = rope->strides[1] * cv.es;
+    pr.q_rope = q_rope;
+    e = mfa::mla_latent_prefill_rope_dispatch(pr, elem_of(prec), Lat, stream);
+  } else {
+    e = mfa::mla_latent_prefill_dispatch(p, elem_of(prec), Lat, stream);
+  }
   if (e == hipErrorNotSupported) return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
   if ((st = hip_status(e, "paged MLA prefill latent attention launch")) != MFA_SUCCESS) return st;
   // mfa_mla_forward_absorbed's output GEMM for B > 1, S_q > 1.
@@ -2769,5 +2789,26 @@ extern "C" mfa_status_t mfa_paged_latent_rope_append_plan(
   return paged_latent_plan(*desc, cache, out, [&](const mfa_paged_latent_cache_t& c) {
     const mfa_paged_rope_cache_t r = plan_rope(rope, c);
     return paged_latent_append(desc, vd, nullptr, nullptr, &c, nullptr, true, vd, nullptr, &r);
+  });
+}
+
+extern "C" mfa_status_t mfa_paged_mla_rope_prefill_forward(
+    const mfa_paged_mla_descriptor_t* desc, const void* query, const void* q_rope, const void* w_k,
+    const void* w_v, const int32_t* new_lens, const mfa_paged_latent_cache_t* cache,
+    const mfa_paged_rope_cache_t* rope, float* output, void* logsumexp, void* stream) {
+  return paged_mla_prefill(desc, query, w_k, w_v, new_lens, cache, output, logsumexp,
+                           (hipStream_t)stream, true, q_rope, rope);
+}
+
+extern "C" mfa_status_t mfa_paged_mla_rope_prefill_plan(const mfa_paged_mla_descriptor_t* desc,
+                                                        const mfa_paged_latent_cache_t* cache,
+                                                        const mfa_paged_rope_cache_t* rope,
+                                                        mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  const void* const vd = (const void*)kPlanDummy;
+  return paged_latent_plan(*desc, cache, out, [&](const mfa_paged_latent_cache_t& c) {
+    const mfa_paged_rope_cache_t r = plan_rope(rope, c);
+    return paged_mla_prefill(desc, vd, vd, vd, nullptr, &c, (float*)kPlanDummy, nullptr, nullptr,
+                             true, vd, &r);
   });
 }

@@ -133,6 +133,9 @@ hipError_t mla_latent_paged_rope_dispatch(const LatentPagedRopeParams& p, int el
 // 16-bit latent-space output in p.c.l.olat (the caller applies W_v).
 hipError_t mla_latent_prefill_dispatch(const LatentPrefillParams& p, int elem, int lat,
                                        hipStream_t stream);
+// ... with the rope key part: mfa_mla_latent_prefill_rope_kernel in that launch's place.
+hipError_t mla_latent_prefill_rope_dispatch(const LatentPrefillRopeParams& p, int elem, int lat,
+                                            hipStream_t stream);
 // Decode (S_q = 1) query projection of the absorbed MLA path; hipErrorNotSupported when the
 // shapes or alignment do not fit (the caller falls back to the general GEMM).
 hipError_t mla_qproj_dispatch(const void* q, const void* wk, void* qt, int B, int H, int D,

@@ -220,6 +220,16 @@ struct LatentPrefillParams {
   const int32_t* new_lens;     // [B] rows of each sequence (clamped to [0, c.l.Sq]); NULL: c.l.Sq
 };
 
+// ... with the rope key part (mfa_mla_latent_prefill_rope_kernel): LatentPagedRopeParams' second
+// view of the pages and the rope part of the query, whose rows q >= n_b are never read.
+struct LatentPrefillRopeParams {
+  LatentPrefillParams c;
+  const void* rope;          // the rope pool (or the latent pool + LAT elements: fused rows)
+  int64_t rope_page_bytes;   // byte stride between its pages
+  int64_t rope_tok_bytes;    // ... and between the token slots of a page
+  const void* q_rope;        // [B][R][64] 16-bit, R = H·S_q as in c.c.l
+};
+
 // General GEMM (gemm_general.hip): any FP32/FP16/BF16 mix, transposes, leading dimensions.
 struct GemmGParams {
   const void* a;

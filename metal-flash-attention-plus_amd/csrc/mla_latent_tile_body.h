@@ -2,9 +2,10 @@
 // (attention_mla_latent.hip), as text.
 //
 // Not a stand-alone header: it is the statements of one iteration of the key loop, included
-// inside mfa_mla_latent_kernel, mfa_mla_latent_paged_kernel, mfa_mla_latent_prefill_kernel and
-// mfa_mla_latent_paged_rope_kernel, between the staging of the next tile's loads and their store to LDS.  The three kernels differ
-// in how a tile reaches LDS and in what leaves the loop (the rope kernel also in one more k-step); the arithmetic on a staged tile, and its
+// inside mfa_mla_latent_kernel, mfa_mla_latent_paged_kernel, mfa_mla_latent_prefill_kernel,
+// mfa_mla_latent_paged_rope_kernel and mfa_mla_latent_prefill_rope_kernel, between the staging of
+// the next tile's loads and their store to LDS.  The kernels differ in how a tile reaches LDS and
+// in what leaves the loop (the two rope kernels also in one more k-step); the arithmetic on a staged tile, and its
 // order, is this text alone, which is what makes their results comparable bit for bit.
 // Contract of the place that includes it:
 //   * a __global__ function template with parameters E and LAT, the constants BK, DS, ND, WS,

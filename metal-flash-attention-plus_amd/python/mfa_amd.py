@@ -659,6 +659,11 @@ _sig("mfa_paged_latent_rope_append", ctypes.c_int,
       _P(PagedLatentCache), _P(PagedRopeCache), _V])
 _sig("mfa_paged_latent_rope_append_plan", ctypes.c_int,
      [_P(PagedLatentAppendDescriptor), _P(PagedLatentCache), _P(PagedRopeCache), _P(KernelPlan)])
+_sig("mfa_paged_mla_rope_prefill_forward", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _V, _V, _V, _V, _V, _P(PagedLatentCache), _P(PagedRopeCache),
+      _V, _V, _V])
+_sig("mfa_paged_mla_rope_prefill_plan", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _P(PagedLatentCache), _P(PagedRopeCache), _P(KernelPlan)])
 _sig("mfa_quantize_workspace_size", ctypes.c_size_t,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32])
 _sig("mfa_quantize", ctypes.c_int,
@@ -1092,6 +1097,29 @@ def paged_latent_rope_append_plan(desc: PagedLatentAppendDescriptor,
     """mfa_paged_latent_rope_append_plan: the kernel paged_latent_rope_append launches.  Needs no
     GPU."""
     return _rope_plan(lib.mfa_paged_latent_rope_append_plan, desc, cache, rope)
+
+
+def paged_mla_rope_prefill_forward(desc: PagedMLADecodeDescriptor, query, q_rope, w_k, w_v,
+                                   cache: PagedLatentCache, rope: PagedRopeCache, output,
+                                   new_lens=None, logsumexp=None, stream=None):
+    """mfa_paged_mla_rope_prefill_forward: paged_mla_prefill_forward with the decoupled RoPE key
+    part — a ragged batch of prompt chunks over a [latent | rope] cache, scores scale * (query
+    W_k^T latent + q_rope k_rope), values from the latent alone.  q_rope [B, H, R, 64] 16-bit,
+    already rotated; its rows q >= n_b, like the query's, are never used.  The default scale is
+    1 / sqrt(head_dim + 64).  lens += n, paged_latent_rope_append and this call can be captured
+    in one graph."""
+    check(lib.mfa_paged_mla_rope_prefill_forward(
+        ctypes.byref(desc), _ptr(query), _ptr(q_rope), _ptr(w_k), _ptr(w_v), _ptr(new_lens),
+        ctypes.byref(cache), ctypes.byref(rope), _ptr(output), _ptr(logsumexp), _stream(stream)))
+
+
+def paged_mla_rope_prefill_plan(desc: PagedMLADecodeDescriptor,
+                                cache: Optional[PagedLatentCache] = None,
+                                rope: Optional[PagedRopeCache] = None) -> list[dict]:
+    """mfa_paged_mla_rope_prefill_plan: the kernels paged_mla_rope_prefill_forward launches (see
+    multihead_plan); without a rope view, a dense rope pool over the cache's pages.  Needs no
+    GPU."""
+    return _rope_plan(lib.mfa_paged_mla_rope_prefill_plan, desc, cache, rope)
 
 
 def quantize(x, target: Precision, mode: QuantMode = QuantMode.tensorWise, rows=None, cols=None,
