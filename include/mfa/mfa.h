@@ -516,7 +516,7 @@ typedef struct mfa_paged_kv_cache {
 
 /* Causal window (MFA_SPARSITY_CAUSAL_WINDOW, window_size = W; no reference counterpart): the
  * local-attention mask of a KV cache, served by mfa_paged_decode_forward (16-bit and INT8 pools,
- * both row forms), mfa_paged_prefill_forward, mfa_quantized_paged_prefill_forward and their three
+ * both row forms) and its row-wise twin mfa_paged_decode_forward_rowwise, mfa_paged_prefill_forward, mfa_quantized_paged_prefill_forward and their three
  * *_plan functions.  Row q sits at key position t_q exactly as under MFA_SPARSITY_CAUSAL (decode:
  * len_b - R + q; prefill: len_b - n_b + q) and attends to keys j with t_q - W <= j <= t_q: W + 1
  * keys, the reference's row > col + window rule joined with the KV-cache causal rule.  W >= 2^30
@@ -616,6 +616,62 @@ mfa_status_t mfa_paged_kv_append(const mfa_paged_append_descriptor_t* desc,
  * 256-key pages in input_precision; NULL pointers inside a cache plan aligned buffers. */
 mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descriptor_t* desc,
                                       const mfa_paged_kv_cache_t* cache, mfa_kernel_plan_t* out);
+
+/* Row-wise INT8 pools: a scale per (token, kv head), computed when the row is written, so the
+ * caller need not know the amax of keys and values that do not exist yet.  The struct goes next
+ * to an INT8 mfa_paged_kv_cache_t whose zero points are 0 (anything else: MFA_ERR_UNSUPPORTED);
+ * the cache struct's k_scale / v_scale are ignored.  A key's value is
+ * k_scales[slot] * q_K, v_scales[slot] * q_V.  Both scale pools share one layout and are indexed
+ * by the cache's page ids and slots. */
+typedef struct mfa_paged_kv_scales {
+  const float* k_scales;   /* device; page p, kv head h, slot t at p*strides[0] + h*strides[1] + t */
+  const float* v_scales;   /* same layout */
+  int64_t strides[2];      /* page, kv head — in floats; slots contiguous; non-negative multiples
+                              of 4 floats; head stride >= page_size; pools 16-byte aligned */
+} mfa_paged_kv_scales_t;
+
+/* mfa_paged_kv_append into row-wise INT8 pools: the same descriptor, addressing, new_lens
+ * raggedness, never-written guarantees and stream behaviour.  Per written (row, kv head), with
+ * a = max_d |x_d| (NaNs ignored): scale = a >= 2^-64 ? a / 127.0f : 1.0f (IEEE FP32 division),
+ * q_d = clamp(round_half_away(x_d / scale), -127, 127), and the scale goes to the slot's entry of
+ * the scale pool (through scales->k_scales / v_scales: the struct's const is the reader's view).
+ * The 2^-64 floor bounds 1 / scale and log2 scale for the reader; rows below it are stored as
+ * zeros with scale 1.  No other scale entry is written.
+ * MFA_ERR_UNSUPPORTED: pools that are not INT8 (INT4 included), non-zero zero points, scale
+ * strides or alignment outside the rules above.  batch_size == 0 or rows == 0 succeeds and
+ * launches nothing.
+ * Row-wise prefill is out of scope: mfa_quantized_paged_prefill_forward stays per-tensor.  A prompt
+ * is prefilled from its 16-bit K/V (mfa_multihead_forward or a 16-bit paged cache) and then
+ * appended row-wise. */
+mfa_status_t mfa_paged_kv_append_rowwise(const mfa_paged_append_descriptor_t* desc,
+                                         const void* key, const void* value,
+                                         const int64_t* key_strides, const int64_t* value_strides,
+                                         const int32_t* new_lens,
+                                         const mfa_paged_kv_cache_t* cache,
+                                         const mfa_paged_kv_scales_t* scales, void* stream);
+/* The kernel that call launches.  cache == NULL plans an INT8 cache of 256-key pages, scales ==
+ * NULL dense scale pools over the cache's pages; NULL pointers inside either plan aligned buffers. */
+mfa_status_t mfa_paged_kv_append_rowwise_plan(const mfa_paged_append_descriptor_t* desc,
+                                              const mfa_paged_kv_cache_t* cache,
+                                              const mfa_paged_kv_scales_t* scales,
+                                              mfa_kernel_plan_t* out);
+
+/* mfa_paged_decode_forward over row-wise INT8 pools: its descriptor, masks (NONE, CAUSAL,
+ * CAUSAL_WINDOW with the page-release contract), dead-row results, clamping rules, split layout,
+ * workspace and merge, attending over the values k_scales[j] * q_K[j], v_scales[j] * q_V[j].
+ * Added safety rule: no scale entry of a slot at or past len_b, or of a page the table does not
+ * name for the keys read, is fetched; a masked key contributes exactly 0.  Scales of the keys read
+ * must be finite and positive (what the row-wise append writes: at least 2^-64 / 127). */
+mfa_status_t mfa_paged_decode_forward_rowwise(const mfa_paged_decode_descriptor_t* desc,
+                                              const void* query, const int64_t* query_strides,
+                                              const mfa_paged_kv_cache_t* cache,
+                                              const mfa_paged_kv_scales_t* scales,
+                                              float* output, void* logsumexp, void* stream);
+/* The kernels that call launches; NULL cache / scales as for the append's plan. */
+mfa_status_t mfa_paged_decode_rowwise_plan(const mfa_paged_decode_descriptor_t* desc,
+                                           const mfa_paged_kv_cache_t* cache,
+                                           const mfa_paged_kv_scales_t* scales,
+                                           mfa_kernel_plan_t* out);
 
 typedef struct mfa_paged_prefill_descriptor {
   mfa_attention_descriptor_t base;   /* precision of Q, scale, sparsity (NONE, CAUSAL or CAUSAL_WINDOW), L precision */

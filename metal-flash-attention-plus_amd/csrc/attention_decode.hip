@@ -380,6 +380,121 @@ __device__ __forceinline__ const char* kv_tile(const PG& pg, const char* head, i
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Row-wise INT8 pools (mfa_paged_decode_forward_rowwise): every key has a K scale and a V scale
+// of its own (PagedKvScales), so the scales cannot fold into c_log2 / o_mul.  The quantised body
+// texts serve them under a switch of the including kernel's scope: RW (constexpr bool), rwsc (the
+// PagedKvScales) and rwstrip (the wave's scale strips in LDS, behind the ring and the merge
+// area).  MFA_DECODE_PER_TENSOR sets the switch off; every `if constexpr (RW)` branch of the
+// texts is then discarded and the per-tensor kernels compile to the code they had.
+//
+// Scale movement.  A tile is 32 keys of one page: two runs of 32 floats.  With the tile's K/V
+// DMA, one tile ahead, the wave issues two dword LDS-DMA loads, lanes 0-31 fetching
+// k_scales[t + lane] into strip[0..31] and then v_scales[t + lane] into strip[64..95] of the
+// tile's strip slot (two slots of kRwStripFloats per wave); lanes 32-63 are out of range in
+// both, fetch nothing and write zeros to strip[32..63] and strip[96..127], which hold nothing
+// then.  Two wave-wide loads with one descriptor live at a time, not one load with the pool
+// picked per half-wave: the two descriptors of a divergent pair cost 9 spilled SGPRs at
+// D = 256.  The scales land in LDS, not in a register: a register filled one loop iteration
+// ahead has to be copied at the loop's end, and the copy waits for the load.  The descriptor
+// covers the keys below min(len, page end), so no scale of an unused slot or of a foreign page
+// is fetched: those lanes read 0.  When the tile is consumed (same vmcnt wait as its K/V, two
+// more operations per tile), lane 32 + j takes v_scales[j] from the strip (1 for a key at or
+// past len), writes lv = log2(vs) to strip[32 + j] and rv = 1 / vs over the scale: two
+// transcendentals per lane and tile.  Every lane then reads the k scale, lv and rv of its own
+// keys back as broadcast ds_read_b128s (four consecutive keys each).  Write and reads are the
+// same wave's, in LDS order: no barrier.
+//
+// Softmax with the V scale inside the max.  x = (s · ks) · c + lv is the log2 of the key's
+// weight times its V scale; the running max m is taken over x, the packed P operand is
+// w = exp2(x - m) = p · vs <= 1 — so the 16-bit P fragment keeps its precision however small the
+// V scales are — and the denominator adds w · rv = exp2(s · ks · c - m) in FP32.  O, l and m are
+// relative to the same m: partials, merge and L = m + log2 l are unchanged, and o_mul is 1.
+constexpr int kRwStripFloats = 128;                      // k scales | lv | v scales, rv | pad
+constexpr int kRwStripBytes = 4 * 2 * kRwStripFloats * 4;  // 4 waves, 2 slots each
+
+#define MFA_DECODE_PER_TENSOR                                                                     \
+  constexpr bool RW = false;                                                                     \
+  const PagedKvScales rwsc{};                                                                    \
+  char* const rwstrip = nullptr;
+
+// One dword per lane by LDS-DMA (lds_dma16's form): base + voff, range-checked against nrec
+// bytes (out of range reads zero), into dst + 4·lane.
+__device__ __forceinline__ void lds_dma4(const void* base, int nrec, int voff, char* dst) {
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  const uint64_t a = (uint64_t)(uintptr_t)base;
+  u32x4 rs;
+  rs[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
+  rs[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
+  rs[2] = __builtin_amdgcn_readfirstlane((unsigned)nrec);
+  rs[3] = 0x00020000u;
+  const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)dst);
+  asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dword %0, %1, 0 offen lds"
+               :
+               :
+               "v"(voff), "s"(rs), "s"(lds)
+               : "memory", "m0");
+}
+
+// The scales of the 32-key tile at key t (wave-uniform) of one pool's kv head (`head` = pool +
+// kvh · head stride) and the bytes of them a load may touch: kv_tile's rule, the keys below both
+// the sequence's length and the page's end.
+template <class PG>
+__device__ __forceinline__ const float* rw_tile(const PG& pg, int64_t page_stride,
+                                                const float* head, int page, int t, int len,
+                                                int* bytes) {
+  if constexpr (PG::paged) {
+    const int pend = ((t >> pg.lg_page) + 1) << pg.lg_page;
+    const int rows = min(min(len, pend) - t, 32);
+    *bytes = rows > 0 ? rows * 4 : 0;
+    const int id = min(max(page, 0), pg.num_pages - 1);
+    return head + (int64_t)id * page_stride + (t & ((1 << pg.lg_page) - 1));
+  } else {
+    *bytes = 0;  // row-wise scales exist for paged caches only
+    return head;
+  }
+}
+
+// The kv head's two scale runs and the page stride, once per kernel.  They are kept in VGPRs
+// (the 32-row D = 256 kernel has no SGPR left: 8 spilled with them there, none without);
+// lds_dma4 reads the tile's base back with v_readfirstlane.
+#define MFA_RW_HEADS                                                                              \
+  uint64_t rwkh = 0, rwvh = 0, rwps = 0;                                                         \
+  if constexpr (RW) {                                                                            \
+    rwkh = (uint64_t)(uintptr_t)(rwsc.k + kvh * rwsc.head);                                      \
+    rwvh = (uint64_t)(uintptr_t)(rwsc.v + kvh * rwsc.head);                                      \
+    rwps = (uint64_t)rwsc.page;                                                                  \
+    asm volatile("" : "+v"(rwkh), "+v"(rwvh), "+v"(rwps));                                       \
+  }
+
+// The tile's two scale runs into its strip slot (see above).
+#define MFA_RW_ISSUE(PAGE, T, SLOT)                                                               \
+  {                                                                                              \
+    int nsc_;                                                                                    \
+    const float* ksp_ = rw_tile(pg, (int64_t)rwps, (const float*)rwkh, PAGE, T, C, &nsc_);       \
+    const float* vsp_ = rw_tile(pg, (int64_t)rwps, (const float*)rwvh, PAGE, T, C, &nsc_);       \
+    asm volatile("" : "+v"(nsc_));                                                               \
+    char* sdst_ = rwstrip + (wave * 2 + (SLOT)) * (kRwStripFloats * 4);                          \
+    const int soff_ = lane < 32 ? 4 * lane : 0x40000000;                                         \
+    lds_dma4(ksp_, nsc_, soff_, sdst_);                                                          \
+    uint64_t vb_ = (uint64_t)(uintptr_t)vsp_;                                                    \
+    asm volatile("" : "+v"(vb_)); /* the second descriptor is built after the first is used */  \
+    lds_dma4((const void*)vb_, nsc_, soff_, sdst_ + 256);                                        \
+  }
+
+// The tile's strip once its loads have landed, with lv and rv derived in place (see above).
+#define MFA_RW_DERIVE(T, SLOT)                                                                    \
+  float* const rwst = reinterpret_cast<float*>(rwstrip) + (wave * 2 + (SLOT)) * kRwStripFloats;  \
+  {                                                                                              \
+    asm volatile("" ::: "memory"); /* the DMA's LDS write is not the compiler's */               \
+    const float raw_ = rwst[lane + 32];                                                          \
+    const float vs_ = (T) + (lane & 31) < C ? raw_ : 1.f;                                        \
+    if (lane >= 32) {                                                                            \
+      rwst[lane] = __builtin_amdgcn_logf(vs_);                                                   \
+      rwst[lane + 32] = __builtin_amdgcn_rcpf(vs_);                                              \
+    }                                                                                            \
+  }
+
 // tile_key(i): first key of this wave's tile i (paged: wave-uniform).  pg0: the page of tile 0;
 // pg1, pg2: the pages of tiles i + 1 and i + 2 while tile i is computed; pg_advance(i) shifts
 // the queue and starts the load for tile i + 3, two steps before that tile's K/V are issued.
@@ -1054,6 +1169,7 @@ __global__ void __launch_bounds__(256, DP >= 256 ? 1 : 2)
   if constexpr (SRC == SRC_SAME) {
     decode32_kv16<E, DP>(dp, pg, smem);
   } else {
+    MFA_DECODE_PER_TENSOR
 #include "decode32_quant_body.h"
   }
 }
@@ -1100,6 +1216,7 @@ __global__ void __launch_bounds__(256, DP == 256 && SRC != SRC_I8 ? 1 : 2)
   if constexpr (SRC == SRC_SAME) {
     decode16_kv16<E, DP>(dp, pg, smem);
   } else {
+    MFA_DECODE_PER_TENSOR
 #include "decode16_quant_body.h"
   }
 }
@@ -1115,8 +1232,41 @@ __global__ void __launch_bounds__(256, DP == 256 && SRC != SRC_I8 ? 1 : 2)
   if constexpr (SRC == SRC_SAME) {
     decode16_kv16<E, DP>(dp, pg, smem);
   } else {
+    MFA_DECODE_PER_TENSOR
 #include "decode16_quant_body.h"
   }
+}
+
+// The two quantised bodies over row-wise INT8 pools ("Row-wise INT8 pools" above): the same
+// texts with the switch on, the scale strips behind the per-tensor kernel's LDS.
+template <class E, int DP>
+__global__ void __launch_bounds__(256, DP >= 256 ? 1 : 2)
+    mfa_fwd_decode_paged_rw_kernel(PagedRwDecodeParams pp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using PG = PagedKvPolicy;
+  constexpr int SRC = SRC_I8;
+  constexpr bool RW = true;
+  PG pg{pp.pg};
+  // D = 256 is one SGPR short with the scales' addressing: the page stride moves to a VGPR
+  // (kv_tile's page offset is then VALU work, read back by the DMA's v_readfirstlane).
+  if constexpr (DP >= 256) asm volatile("" : "+v"(pg.page_bytes));
+  const DecodeParams& dp = pp.d;
+  const PagedKvScales& rwsc = pp.sc;
+  char* const rwstrip = smem + decode32_lds<DP>();
+#include "decode32_quant_body.h"
+}
+
+template <class E, int DP>
+__global__ void __launch_bounds__(256, 2) mfa_fwd_decode16_paged_rw_kernel(PagedRwDecodeParams pp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using PG = PagedKvPolicy;
+  constexpr int SRC = SRC_I8;
+  constexpr bool RW = true;
+  const PG pg{pp.pg};
+  const DecodeParams& dp = pp.d;
+  const PagedKvScales& rwsc = pp.sc;
+  char* const rwstrip = smem + decode16_lds<DP, SRC_I8>();
+#include "decode16_quant_body.h"
 }
 
 // One query row per wave: combines the row's nsplit partials.  O is written with the
@@ -1342,6 +1492,53 @@ hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int 
   MFA_DECP(P_BF16, BF16, 128)
   MFA_DECP(P_BF16, BF16, 256)
 #undef MFA_DECP
+  return launch_merge(e, pp.d, stream);
+}
+
+// The row-wise 16-row kernel exists below D = 256 only (see the dispatcher).
+template <class E, int DP>
+static hipError_t launch_rw16(dim3 grid, const PagedRwDecodeParams& pp, hipStream_t stream) {
+  if constexpr (DP < 256)
+    return launch(mfa_fwd_decode16_paged_rw_kernel<E, DP>, grid, dim3(256),
+                  decode16_lds<DP, SRC_I8>() + kRwStripBytes, stream, pp);
+  else
+    return hipErrorNotSupported;
+}
+
+// The row-wise twin: INT8 pools with a scale per (key, kv head) in `sc`; the same layout,
+// workspace and merge.  The caller has set the zero points to 0, c_log2 without a K scale and
+// o_mul = 1.
+hipError_t fwd_decode_paged_rw_dispatch(const FwdParams& p, const PagedKv& pg,
+                                        const PagedKvScales& sc, int elem, void* workspace,
+                                        hipStream_t stream) {
+  if (p.k.prec != P_INT8 || p.v.prec != P_INT8 || p.k.ss != p.v.ss) return hipErrorNotSupported;
+  PagedRwDecodeParams pp;
+  pp.pg = pg;
+  pp.sc = sc;
+  const DecodeLaunch dl = decode_params(
+      p, p.C, decode_paged_span(p.C, p.R, p.mask.window, p.mask.window_size), workspace, &pp.d);
+  if (dl.err != hipSuccess) return dl.err;
+  const dim3 grid = dl.grid;
+  const int DP = dl.DP;
+  hipError_t e = hipErrorNotSupported;
+  // D = 256 takes the 32-row form for any row count: the per-tensor INT8 16-row kernel fills its
+  // 256 registers there (kv_split_start), and the 24 more the scales need would spill.
+  const bool rows16 = pp.d.rows <= 16;
+#define MFA_DECRW(ELEM, EE, DPV)                                                               \
+  if (elem == ELEM && DP == DPV) {                                                             \
+    if (rows16 && DPV < 256)                                                                   \
+      e = launch_rw16<EE, DPV>(grid, pp, stream);                                              \
+    else                                                                                       \
+      e = launch(mfa_fwd_decode_paged_rw_kernel<EE, DPV>, grid, dim3(256),                     \
+                 decode32_lds<DPV>() + kRwStripBytes, stream, pp);                             \
+  }
+  MFA_DECRW(P_FP16, F16, 64)
+  MFA_DECRW(P_FP16, F16, 128)
+  MFA_DECRW(P_FP16, F16, 256)
+  MFA_DECRW(P_BF16, BF16, 64)
+  MFA_DECRW(P_BF16, BF16, 128)
+  MFA_DECRW(P_BF16, BF16, 256)
+#undef MFA_DECRW
   return launch_merge(e, pp.d, stream);
 }
 

@@ -7,7 +7,9 @@
 //     width) and SRC (SRC_I8 or SRC_I4);
 //   * a type PG in scope, the addressing policy (ContiguousKv or PagedKvPolicy), and an object
 //     `pg` of it;
-//   * `dp`, a DecodeParams (or a reference to one), and `smem`, the dynamic LDS array.
+//   * `dp`, a DecodeParams (or a reference to one), and `smem`, the dynamic LDS array;
+//   * the row-wise switch: RW, rwsc and rwstrip (attention_decode.hip, "Row-wise INT8 pools";
+//     MFA_DECODE_PER_TENSOR for the per-tensor kernels).  RW needs a paged INT8 cache.
 // It ends the kernel: nothing may follow it but the closing braces.  It defines and undefines
 // DEC16_KLOAD and DEC16_STEP.
 //
@@ -31,7 +33,9 @@
   constexpr int CPR = ROWBS / 16;           // 16-byte chunks per row
   constexpr int KLB = ROWBS / 4;            // K bytes per lane per 16-key block
   constexpr int NKL = KLB >= 16 ? KLB / 16 : 1;  // K loads per block (b128, or one b64)
-  constexpr int NI = NPV + NKB * NKL;       // vm operations per tile
+  static_assert(!RW || (PG::paged && !I4), "row-wise scales: paged INT8 caches");
+  constexpr int NSC = RW ? 2 : 0;           // scale loads per tile, issued with its K loads
+  constexpr int NI = NPV + NKB * NKL + NSC; // vm operations per tile
   static_assert(DP == 64 || DP == 128 || DP == 256, "decode16 widths");
 
   const int tid = threadIdx.x;
@@ -119,14 +123,18 @@
     vtrow = key * ROWBS + (I4 ? 0 : 8 * (l16 & 1));
     vtsw = vsw(key);
   }
-  const float zk = (float)(p.k.zp + (I4 ? 8 : 0)), zv = (float)(p.v.zp + (I4 ? 8 : 0));
+  // (Row-wise pools are symmetric: the host admits zero points of 0 only.)
+  const float zk = RW ? 0.f : (float)(p.k.zp + (I4 ? 8 : 0)),
+              zv = RW ? 0.f : (float)(p.v.zp + (I4 ? 8 : 0));
 
+  MFA_RW_HEADS
   uint32_t ka[NKB][KLB / 4], kn[NKB][KLB / 4];
 #define DEC16_KLOAD(KR, TI, PAGE)                                                                 \
   {                                                                                              \
     int nb_;                                                                                     \
     const char* tp_ =                                                                            \
         kv_tile(pg, khead, PAGE, tile_key(TI), C, ssb, p.D >> SH, kbytes, &nb_);                 \
+    if constexpr (RW) MFA_RW_ISSUE(PAGE, tile_key(TI), (TI) & 1)                                 \
     const __amdgpu_buffer_rsrc_t rs_ =                                                           \
         __builtin_amdgcn_make_buffer_rsrc((void*)tp_, (short)0, nb_, 0x00020000);                \
     _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) {                                         \
@@ -191,6 +199,20 @@
           sc[kb] = mma16<E>(widen_i8<E>(KC[kb][2 * dt], KC[kb][2 * dt + 1], zk), qf[dt], sc[kb]); \
       }                                                                                          \
     }                                                                                            \
+    /* Row-wise: x = (s · ks) · c + lv per key, before the mask; rv[] stays for the sum. */      \
+    float4 rv[NKB];                                                                              \
+    if constexpr (RW) {                                                                          \
+      MFA_RW_DERIVE(t, ii & 1)                                                                   \
+      _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb) {                                       \
+        const float4 ks = *reinterpret_cast<const float4*>(rwst + 16 * kb + 4 * g);              \
+        const float4 lv = *reinterpret_cast<const float4*>(rwst + 32 + 16 * kb + 4 * g);         \
+        rv[kb] = *reinterpret_cast<const float4*>(rwst + 64 + 16 * kb + 4 * g);                  \
+        sc[kb][0] = __builtin_fmaf(sc[kb][0] * ks.x, c, lv.x);                                   \
+        sc[kb][1] = __builtin_fmaf(sc[kb][1] * ks.y, c, lv.y);                                   \
+        sc[kb][2] = __builtin_fmaf(sc[kb][2] * ks.z, c, lv.z);                                   \
+        sc[kb][3] = __builtin_fmaf(sc[kb][3] * ks.w, c, lv.w);                                   \
+      }                                                                                          \
+    }                                                                                            \
     if (t + BK > k1 || (p.mask.causal && t + BK - 1 > qcol) || t < wlo) {                       \
       const int last = (p.mask.causal ? min(k1 - 1, qcol) : k1 - 1) - t, first = wlo - t;        \
       _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb)                                         \
@@ -202,7 +224,8 @@
     float mx = fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3]));                      \
     _Pragma("unroll") for (int kb = 1; kb < NKB; ++kb)                                           \
       _Pragma("unroll") for (int e = 0; e < 4; ++e) mx = fmaxf(mx, sc[kb][e]);                   \
-    mx = xgroup_max(mx) * c;                                                                     \
+    mx = xgroup_max(mx);                                                                         \
+    if constexpr (!RW) mx *= c;                                                                  \
     if (__any(mx > m)) {                                                                         \
       const float m_new = fmaxf(m, mx);                                                          \
       const float corr = __builtin_amdgcn_exp2f(m - m_new);                                      \
@@ -213,9 +236,14 @@
     float rs = 0.f;                                                                              \
     _Pragma("unroll") for (int kb = 0; kb < NKB; ++kb)                                           \
       _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                            \
-        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kb][e], c, -m));               \
+        const float pv =                                                                         \
+            __builtin_amdgcn_exp2f(RW ? sc[kb][e] - m : __builtin_fmaf(sc[kb][e], c, -m));       \
         sc[kb][e] = pv;                                                                          \
-        rs += pv;                                                                                \
+        if constexpr (RW)                                                                        \
+          rs = __builtin_fmaf(pv, e == 0 ? rv[kb].x : e == 1 ? rv[kb].y : e == 2 ? rv[kb].z      \
+                                                                             : rv[kb].w, rs);   \
+        else                                                                                     \
+          rs += pv;                                                                              \
       }                                                                                          \
     lh += rs;                                                                                    \
     i16x8 pb[NKB / 2];                                                                           \

@@ -9,7 +9,9 @@
 //     width) and SRC (SRC_I8 or SRC_I4);
 //   * a type PG in scope, the addressing policy (ContiguousKv or PagedKvPolicy), and an object
 //     `pg` of it;
-//   * `dp`, a DecodeParams (or a reference to one), and `smem`, the dynamic LDS array.
+//   * `dp`, a DecodeParams (or a reference to one), and `smem`, the dynamic LDS array;
+//   * the row-wise switch: RW, rwsc and rwstrip (attention_decode.hip, "Row-wise INT8 pools";
+//     MFA_DECODE_PER_TENSOR for the per-tensor kernels).  RW needs a paged INT8 cache.
 // It ends the kernel: nothing may follow it but the closing braces.
 //
 // Why text and not a function: the same statements lifted into a __device__ __forceinline__
@@ -21,6 +23,8 @@
   const FwdParams& p = dp.f;
   constexpr bool I4 = SRC == SRC_I4;
   static_assert(!(PG::paged && I4), "paged caches: 16-bit and INT8");
+  static_assert(!RW || (PG::paged && !I4), "row-wise scales: paged INT8 caches");
+  constexpr int NSC = RW ? 2 : 0;           // scale loads per tile (vm operations)
   // INT4 keeps three tiles in flight (four ring slots in the INT8 ring's bytes: the packed
   // tiles are half as large, and V is read from the packed tile too).
   constexpr int BK = 32, NSLOT = SRC == SRC_I4 ? 4 : 2, ND = DP / 32;
@@ -46,7 +50,9 @@
   const int rt = u % dp.nrt;
   const int bk = u / dp.nrt;
   const int kvh = bk % p.Hkv, b = bk / p.Hkv;
-  const float c = p.c_log2;
+  float c = p.c_log2;
+  // (Row-wise: kept in a VGPR, with the scale heads below; the D = 256 kernel is out of SGPRs.)
+  if constexpr (RW) asm volatile("" : "+v"(c));
   const int C = kv_len(p, pg, b);
 
   // The lane's query row of this tile: row = g·R + q of kv head kvh's group (h = kvh + g·H_kv).
@@ -110,6 +116,7 @@
                       (PG::paged ? 0 : ((int64_t)b * p.v.sb + (int64_t)kvh * p.v.sh) >> SH);
   const int kbytes = (int)((int64_t)(C - 1) * ssb + (p.D >> SH));
   const int vbytes = (int)((int64_t)(C - 1) * (p.v.ss >> SH) + (p.D >> SH));
+  MFA_RW_HEADS
   auto issue = [&](int i, int slot, int page) {
     const int t = tile_key(i);
     char* kdst = ring + slot * 2 * TILEBS;
@@ -121,6 +128,8 @@
     for (int n = 0; n < NPC; ++n) lds_dma16(kp, nk, poff[n], kdst + n * 1024);
 #pragma unroll
     for (int n = 0; n < NPC; ++n) lds_dma16(vp, nv, voff[n], kdst + TILEBS + n * 1024);
+    // (Last: the K/V descriptors are dead by now, and the D = 256 kernel has no SGPR to spare.)
+    if constexpr (RW) MFA_RW_ISSUE(page, t, slot)
   };
   // ds_read_b64_tr_b8 lanes (see attention_fwd_i8.hip): in each 16-lane group, lane 2j supplies
   // the row of key acc_row(j + 8s, hh) and receives column d0 + (lane & 15) of the 8 rows.
@@ -142,7 +151,9 @@
     v4off = key * ROWBS + 8 * ((lane >> 4) & 1);
     v4sw = swz4(key);
   }
-  const float zk = (float)(p.k.zp + (I4 ? 8 : 0)), zv = (float)(p.v.zp + (I4 ? 8 : 0));
+  // (Row-wise pools are symmetric: the host admits zero points of 0 only.)
+  const float zk = RW ? 0.f : (float)(p.k.zp + (I4 ? 8 : 0)),
+              zv = RW ? 0.f : (float)(p.v.zp + (I4 ? 8 : 0));
 
   f32x16 o[ND];
 #pragma unroll
@@ -158,7 +169,7 @@
     if (i + NSLOT - 1 < mine) {
       issue(i + NSLOT - 1, (i + NSLOT - 1) % NSLOT, pg1);
       pg_advance(i);
-      __builtin_amdgcn_s_waitcnt(vm_wait((NSLOT - 1) * 2 * NPC));  // tile i landed
+      __builtin_amdgcn_s_waitcnt(vm_wait((NSLOT - 1) * (2 * NPC + NSC)));  // tile i landed
     } else if (NSLOT >= 4 && i + 2 < mine) {
       __builtin_amdgcn_s_waitcnt(vm_wait(4 * NPC));  // tiles i + 1, i + 2 still in flight
     } else if (NSLOT >= 3 && i + 1 < mine) {
@@ -190,6 +201,22 @@
         sa[0] = E::mma(widen_i8<E>(kb.x, kb.y, zk), qf[st], sa[0]);
       }
     }
+    // Row-wise: x = (s · ks) · c + lv per key, before the mask (a key past C has ks = 0 and
+    // lv = 0); rv[] stays for the denominator.
+    float4 rv[4];
+    if constexpr (RW) {
+      MFA_RW_DERIVE(t, slot)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 ks = *reinterpret_cast<const float4*>(rwst + 8 * g + 4 * hh);
+        const float4 lv = *reinterpret_cast<const float4*>(rwst + 32 + 8 * g + 4 * hh);
+        rv[g] = *reinterpret_cast<const float4*>(rwst + 64 + 8 * g + 4 * hh);
+        sa[0][4 * g] = __builtin_fmaf(sa[0][4 * g] * ks.x, c, lv.x);
+        sa[0][4 * g + 1] = __builtin_fmaf(sa[0][4 * g + 1] * ks.y, c, lv.y);
+        sa[0][4 * g + 2] = __builtin_fmaf(sa[0][4 * g + 2] * ks.z, c, lv.z);
+        sa[0][4 * g + 3] = __builtin_fmaf(sa[0][4 * g + 3] * ks.w, c, lv.w);
+      }
+    }
     if (t + BK > C || (p.mask.causal && t + BK - 1 > qcol) || t < wlo) {
       // Keys past C, (causal) keys past the lane's query index and (window) keys below
       // qcol - window: -inf (key offset acc_row(r, hh) within the tile).
@@ -200,7 +227,8 @@
     float mx = s[0];
 #pragma unroll
     for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-    mx = cross_half_max(mx) * c;
+    mx = cross_half_max(mx);
+    if constexpr (!RW) mx *= c;
     if (__any(mx > m)) {
       const float m_new = fmaxf(m, mx);
       const float corr = __builtin_amdgcn_exp2f(m - m_new);
@@ -214,9 +242,14 @@
     float rs = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c, -m));
+      const float pv = __builtin_amdgcn_exp2f(RW ? s[r] - m : __builtin_fmaf(s[r], c, -m));
       s[r] = pv;
-      rs += pv;
+      if constexpr (RW) {
+        const float4 v4 = rv[r >> 2];
+        rs = __builtin_fmaf(pv, (r & 3) == 0 ? v4.x : (r & 3) == 1 ? v4.y : (r & 3) == 2 ? v4.z : v4.w, rs);
+      } else {
+        rs += pv;
+      }
     }
     lh += rs;
     i16x8 pb[2];

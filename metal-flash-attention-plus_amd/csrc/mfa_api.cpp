@@ -1957,6 +1957,46 @@ mfa_status_t paged_cache_buffers(const char* what, const mfa_paged_kv_cache_t& c
   return MFA_SUCCESS;
 }
 
+// Row-wise INT8 pools: the cache must be INT8 with zero points 0 (its k_scale / v_scale are
+// ignored), and the scales struct, where there is one, keeps its stride rules.  Applied right
+// after the cache view; `scales` may still be null here (an empty call may pass none).
+mfa_status_t paged_rowwise_view(const char* what, const mfa_paged_kv_cache_t& c,
+                                const PagedCacheView& v, const mfa_paged_kv_scales_t* scales) {
+  if (!v.i8)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: row-wise scales need INT8 pools (precision %d)", what,
+                v.cprec);
+  if (c.k_zero_point != 0 || c.v_zero_point != 0)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: row-wise pools are symmetric (zero points %d, %d)", what,
+                c.k_zero_point, c.v_zero_point);
+  if (!scales) return MFA_SUCCESS;
+  for (int i = 0; i < 2; ++i)
+    if (scales->strides[i] < 0 || scales->strides[i] % 4 != 0)
+      return fail(MFA_ERR_UNSUPPORTED, "%s: scale stride %d is not a multiple of 4 floats", what, i);
+  if (scales->strides[1] < (int64_t)c.page_size)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: scale head stride %lld is below the page size", what,
+                (long long)scales->strides[1]);
+  return MFA_SUCCESS;
+}
+
+// ... and after the empty call's exit and the cache's buffers: the two scale pools.
+mfa_status_t paged_rowwise_buffers(const char* what, const mfa_paged_kv_scales_t* scales,
+                                   mfa::PagedKvScales* out) {
+  if (!scales || !scales->k_scales || !scales->v_scales)
+    return fail(MFA_ERR_INVALID_ARGUMENT, "%s requires the scales struct and both scale pools", what);
+  if (!aligned16(scales->k_scales) || !aligned16(scales->v_scales))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: scale pools must be 16-byte aligned", what);
+  out->k = scales->k_scales; out->v = scales->v_scales;
+  out->page = scales->strides[0]; out->head = scales->strides[1];
+  return MFA_SUCCESS;
+}
+
+// The scales argument of a row-wise entry point (null: the per-tensor call); sc: the checked
+// pools, filled by paged_rowwise_buffers.
+struct RowwiseArg {
+  const mfa_paged_kv_scales_t* scales;
+  mfa::PagedKvScales sc;
+};
+
 // The pools as the K / V operands of a forward: only ptr, the token stride, precision and zero
 // point are read.
 void paged_pool_operands(const mfa_paged_kv_cache_t& c, const PagedCacheView& v, int D,
@@ -2037,7 +2077,7 @@ template <class Desc, class Limits, class Launch>
 mfa_status_t paged_kv_forward(const char* what, const Desc* desc, const void* query,
                               const int64_t* query_strides, const mfa_paged_kv_cache_t* cache,
                               float* output, void* logsumexp, hipStream_t stream, bool allow_i8,
-                              Limits limits, Launch launch) {
+                              Limits limits, Launch launch, RowwiseArg* rw = nullptr) {
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const mfa_attention_descriptor_t& base = desc->base;
   const int64_t B = desc->batch_size, H = desc->num_heads, Hkv = desc->num_kv_heads;
@@ -2056,19 +2096,22 @@ mfa_status_t paged_kv_forward(const char* what, const Desc* desc, const void* qu
   mfa_status_t st =
       paged_cache_view(what, *cache, B, D, desc->max_seq_len, qprec, "query's", allow_i8, &cv);
   if (st != MFA_SUCCESS) return st;
+  if (rw && (st = paged_rowwise_view(what, *cache, cv, rw->scales)) != MFA_SUCCESS) return st;
   if (!paged_kv_mask_served(base))
     return fail(MFA_ERR_UNSUPPORTED, "%s: masks other than causal and the causal window", what);
   if ((st = check_transposes(base, false, what)) != MFA_SUCCESS) return st;
   const float scale = resolve_scale(base, (int)D);
   // One rule and one association for decode and prefill: (log2 e · scale) · k_scale, so the two
   // calls give an INT8 pool the same bits.
-  const float fk = cv.i8 ? cache->k_scale : 1.f, fv = cv.i8 ? cache->v_scale : 1.f;
+  // (Row-wise: the scales are the kernel's, per key.)
+  const float fk = cv.i8 && !rw ? cache->k_scale : 1.f, fv = cv.i8 && !rw ? cache->v_scale : 1.f;
   if (!(scale > 0.f) || !(fk > 0.f) || !(1.442695041f * scale * fk > 0.f))
     return fail(MFA_ERR_UNSUPPORTED, "%s: non-positive scale", what);
   if ((st = limits(B, H, Hkv, R)) != MFA_SUCCESS) return st;
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
   if ((st = paged_cache_buffers(what, *cache, "query, output", query && output)) != MFA_SUCCESS)
     return st;
+  if (rw && (st = paged_rowwise_buffers(what, rw->scales, &rw->sc)) != MFA_SUCCESS) return st;
 
   mfa::FwdParams p;
   memset(&p, 0, sizeof(p));
@@ -2095,8 +2138,9 @@ mfa_status_t paged_kv_forward(const char* what, const Desc* desc, const void* qu
 // or under the causal window the window (decode_paged_span).
 mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void* query,
                           const int64_t* query_strides, const mfa_paged_kv_cache_t* cache,
-                          float* output, void* logsumexp, hipStream_t stream) {
-  const char* const what = "paged decode";
+                          float* output, void* logsumexp, hipStream_t stream,
+                          RowwiseArg* rw = nullptr) {
+  const char* const what = rw ? "row-wise paged decode" : "paged decode";
   return paged_kv_forward(
       what, desc, query, query_strides, cache, output, logsumexp, stream, true,
       [&](int64_t B, int64_t H, int64_t Hkv, int64_t R) -> mfa_status_t {
@@ -2115,11 +2159,13 @@ mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void*
         const size_t wsb = mfa::decode_workspace_bytes(p.B, p.Hkv, p.H / p.Hkv * p.R, span, p.D);
         if (wsb && mfa::plan_capture()) ws = (void*)kPlanDummy;
         else if (wsb && (st = scratch(wsb, &ws, 15, stream)) != MFA_SUCCESS) return st;
-        const hipError_t e = mfa::fwd_decode_paged_dispatch(p, cv.pg, elem, ws, stream);
+        const hipError_t e = rw ? mfa::fwd_decode_paged_rw_dispatch(p, cv.pg, rw->sc, elem, ws, stream)
+                                : mfa::fwd_decode_paged_dispatch(p, cv.pg, elem, ws, stream);
         if (e == hipErrorNotSupported)
           return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
         return hip_status(e, "mfa_fwd (paged decode) launch");
-      });
+      },
+      rw);
 }
 
 // The write side (paged_append.hip): new key / value rows to their slots in the pools, addressed
@@ -2128,8 +2174,9 @@ mfa_status_t paged_decode(const mfa_paged_decode_descriptor_t* desc, const void*
 mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void* key,
                           const void* value, const int64_t* key_strides,
                           const int64_t* value_strides, const int32_t* new_lens,
-                          const mfa_paged_kv_cache_t* cache, hipStream_t stream) {
-  const char* const what = "paged append";
+                          const mfa_paged_kv_cache_t* cache, hipStream_t stream,
+                          RowwiseArg* rw = nullptr) {
+  const char* const what = rw ? "row-wise paged append" : "paged append";
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const int64_t B = desc->batch_size, Hkv = desc->num_kv_heads;
   const int64_t R = desc->rows, D = desc->head_dim;
@@ -2143,8 +2190,9 @@ mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void*
   mfa_status_t st =
       paged_cache_view(what, *cache, B, D, desc->max_seq_len, iprec, "input's", true, &cv);
   if (st != MFA_SUCCESS) return st;
+  if (rw && (st = paged_rowwise_view(what, *cache, cv, rw->scales)) != MFA_SUCCESS) return st;
   // The kernel divides by the scales: stricter than the readers' rule.
-  if (cv.i8)
+  if (cv.i8 && !rw)
     for (const float s : {cache->k_scale, cache->v_scale})
       if (!(s > 0.f) || !std::isfinite(s))
         return fail(MFA_ERR_UNSUPPORTED, "%s: scale %g is not finite and positive", what, (double)s);
@@ -2153,6 +2201,7 @@ mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void*
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to write; the buffers may be null
   if ((st = paged_cache_buffers(what, *cache, "key, value", key && value)) != MFA_SUCCESS)
     return st;
+  if (rw && (st = paged_rowwise_buffers(what, rw->scales, &rw->sc)) != MFA_SUCCESS) return st;
 
   mfa::PagedAppendParams p;
   memset(&p, 0, sizeof(p));
@@ -2180,6 +2229,17 @@ mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void*
   p.Hkv = (int)Hkv; p.R = (int)R; p.D = (int)D;
   p.cap = (int)cv.cap;
   p.rows_total = (int)(B * R);
+  if (rw) {
+    mfa::PagedAppendRwParams pr;
+    const mfa::PagedKvScales& sc = rw->sc;
+    pr.a = p;
+    pr.scales[0] = const_cast<float*>(sc.k); pr.scales[1] = const_cast<float*>(sc.v);
+    pr.sc_page = sc.page; pr.sc_head = sc.head;
+    pr.lg_group = 0;
+    while ((16 << pr.lg_group) < D) ++pr.lg_group;  // next_pow2(D / 16) lanes own a head row
+    return hip_status(mfa::paged_append_rowwise_dispatch(pr, iprec, stream),
+                      "mfa_paged_kv_append_rowwise launch");
+  }
   return hip_status(mfa::paged_append_dispatch(p, iprec, cv.i8, 2, stream),
                     "mfa_paged_kv_append launch");
 }
@@ -2652,6 +2712,65 @@ extern "C" mfa_status_t mfa_paged_kv_append_plan(const mfa_paged_append_descript
   return paged_plan(*desc, desc->input_precision, cache, out, [&](const mfa_paged_kv_cache_t& c) {
     return paged_append(desc, (const void*)kPlanDummy, (const void*)kPlanDummy, nullptr, nullptr,
                         nullptr, &c, nullptr);
+  });
+}
+
+// The scales struct of a row-wise plan query: the given one with its null pools replaced or,
+// without one, dense pools over the cache's pages.
+static mfa_paged_kv_scales_t plan_scales(const mfa_paged_kv_scales_t* scales,
+                                         const mfa_paged_kv_cache_t& c, uint32_t kv_heads) {
+  mfa_paged_kv_scales_t s;
+  if (scales) {
+    s = *scales;
+  } else {
+    memset(&s, 0, sizeof(s));
+    s.strides[1] = c.page_size;
+    s.strides[0] = (int64_t)c.page_size * kv_heads;
+  }
+  fill_dummy(s.k_scales); fill_dummy(s.v_scales);
+  return s;
+}
+
+extern "C" mfa_status_t mfa_paged_kv_append_rowwise(
+    const mfa_paged_append_descriptor_t* desc, const void* key, const void* value,
+    const int64_t* key_strides, const int64_t* value_strides, const int32_t* new_lens,
+    const mfa_paged_kv_cache_t* cache, const mfa_paged_kv_scales_t* scales, void* stream) {
+  RowwiseArg rw{scales, {}};
+  return paged_append(desc, key, value, key_strides, value_strides, new_lens, cache,
+                      (hipStream_t)stream, &rw);
+}
+
+extern "C" mfa_status_t mfa_paged_kv_append_rowwise_plan(
+    const mfa_paged_append_descriptor_t* desc, const mfa_paged_kv_cache_t* cache,
+    const mfa_paged_kv_scales_t* scales, mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return paged_plan(*desc, MFA_PRECISION_INT8, cache, out, [&](const mfa_paged_kv_cache_t& c) {
+    const mfa_paged_kv_scales_t s = plan_scales(scales, c, desc->num_kv_heads);
+    RowwiseArg rw{&s, {}};
+    return paged_append(desc, (const void*)kPlanDummy, (const void*)kPlanDummy, nullptr, nullptr,
+                        nullptr, &c, nullptr, &rw);
+  });
+}
+
+extern "C" mfa_status_t mfa_paged_decode_forward_rowwise(
+    const mfa_paged_decode_descriptor_t* desc, const void* query, const int64_t* query_strides,
+    const mfa_paged_kv_cache_t* cache, const mfa_paged_kv_scales_t* scales, float* output,
+    void* logsumexp, void* stream) {
+  RowwiseArg rw{scales, {}};
+  return paged_decode(desc, query, query_strides, cache, output, logsumexp, (hipStream_t)stream,
+                      &rw);
+}
+
+extern "C" mfa_status_t mfa_paged_decode_rowwise_plan(const mfa_paged_decode_descriptor_t* desc,
+                                                      const mfa_paged_kv_cache_t* cache,
+                                                      const mfa_paged_kv_scales_t* scales,
+                                                      mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return paged_plan(*desc, MFA_PRECISION_INT8, cache, out, [&](const mfa_paged_kv_cache_t& c) {
+    const mfa_paged_kv_scales_t s = plan_scales(scales, c, desc->num_kv_heads);
+    RowwiseArg rw{&s, {}};
+    return paged_decode(desc, (const void*)kPlanDummy, nullptr, &c, (float*)kPlanDummy, nullptr,
+                        nullptr, &rw);
   });
 }
 

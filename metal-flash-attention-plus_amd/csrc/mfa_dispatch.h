@@ -77,6 +77,11 @@ hipError_t fwd_decode_dispatch(const FwdParams& p, int elem, void* workspace, hi
 int decode_paged_span(int cap, int R, bool window, uint32_t window_size);
 hipError_t fwd_decode_paged_dispatch(const FwdParams& p, const PagedKv& pg, int elem,
                                      void* workspace, hipStream_t stream);
+// ... over row-wise INT8 pools: a scale per (key, kv head) in `sc`; p.k.zp = p.v.zp = 0, p.c_log2
+// without a K scale, p.o_mul = 1.  Layout, workspace and merge as above.
+hipError_t fwd_decode_paged_rw_dispatch(const FwdParams& p, const PagedKv& pg,
+                                        const PagedKvScales& sc, int elem, void* workspace,
+                                        hipStream_t stream);
 // Ragged multi-row forward over the same cache, 16-bit pools of the compute type `elem`
 // (attention_prefill_paged.hip): one launch of 128-row query blocks, no workspace.  p.R is the
 // rows per sequence in the query, p.C the cap on every length; new_lens: device [B] or NULL.
@@ -92,6 +97,10 @@ hipError_t fwd_prefill_paged_kv8_dispatch(const FwdParams& p, const PagedKv& pg,
 // pool of mfa_paged_latent_append, one "head" of kv_latent_dim elements).
 hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8, int operands,
                                  hipStream_t stream);
+// Key and value rows into row-wise INT8 pools, each (row, kv head) with its own amax / 127 scale
+// stored in the scale pools (mfa_paged_append_rowwise_kernel).
+hipError_t paged_append_rowwise_dispatch(const PagedAppendRwParams& p, int elem,
+                                         hipStream_t stream);
 // The latent row and its 64-element rope key row to slot t of the same page, one launch
 // (mfa_paged_latent_rope_append); 16-bit rows of either type, the bits unchanged.
 hipError_t paged_rope_append_dispatch(const PagedRopeAppendParams& p, hipStream_t stream);

@@ -117,6 +117,21 @@ struct PagedDecodeParams {
   PagedKv pg;
 };
 
+// Row-wise INT8 pools (mfa_paged_kv_scales_t): one FP32 scale per (token slot, kv head) next to
+// each pool; page p, kv head h, slot t at p·page + h·head + t.
+struct PagedKvScales {
+  const float* k;
+  const float* v;
+  int64_t page, head;          // strides in floats; the slots of a head are contiguous
+};
+// The row-wise decode kernels (mfa_fwd_decode_paged_rw_kernel, mfa_fwd_decode16_paged_rw_kernel):
+// d.f.k.zp = d.f.v.zp = 0, d.f.c_log2 carries no K scale and d.f.o_mul is 1.
+struct PagedRwDecodeParams {
+  DecodeParams d;
+  PagedKv pg;
+  PagedKvScales sc;
+};
+
 // Paged prefill (attention_prefill_paged.hip): f.R query rows per sequence attend to the paged
 // cache, row q < n_b of batch item b at key position len_b - n_b + q.
 struct PagedPrefillParams {
@@ -138,6 +153,15 @@ struct PagedAppendParams {
   int32_t Hkv, R, D;
   int32_t cap;                 // positions at or past it are dropped: min(max_seq_len, table span)
   int32_t rows_total;          // B · R
+};
+
+// Row-wise append (mfa_paged_append_rowwise_kernel): a's INT8 pools with a.scale / a.zp unused;
+// each written (row, kv head) gets scale = amax / 127 in scales[] (PagedKvScales' layout).
+struct PagedAppendRwParams {
+  PagedAppendParams a;
+  float* scales[2];            // key, value
+  int64_t sc_page, sc_head;    // strides in floats
+  int32_t lg_group;            // log2 of the lanes that own one head row: next_pow2(D / 16)
 };
 
 // Append to a paged latent cache with its rope part (paged_append.hip,

@@ -14,6 +14,9 @@
 // mfa_paged_latent_rope_append has a kernel of its own below: two operands of different widths
 // (the latent row and its 64-element rope key row) into two views of the same pages.
 //
+// mfa_paged_kv_append_rowwise has a kernel of its own as well (mfa_paged_append_rowwise_kernel):
+// INT8 pools with one scale per written (row, kv head), computed from the row as it is written.
+//
 // Memory-bound, one launch for K and V (blockIdx.y picks the operand).  A wave owns one
 // (sequence, row) at a time: length, row count and block-table entry are uniform loads on the
 // scalar path and the position, page and both base addresses are formed once per row; the lanes
@@ -116,6 +119,101 @@ __global__ __launch_bounds__(64 * kAppendWaves) void mfa_paged_append_kernel(Pag
       }
     }
   }
+}
+
+// Row-wise INT8 pools (mfa_paged_kv_append_rowwise): every written (row, kv head) is quantised
+// with a scale of its own, amax / 127, stored in the slot's entry of a scale pool.  The skeleton
+// is mfa_paged_append_kernel's (a wave per (sequence, row), scalar-path addressing, blockIdx.y the
+// operand); what differs is that a head row must be reduced before it can be written:
+//   * a head row belongs to a group of G = next_pow2(D / 16) adjacent lanes (1 .. 16), so a pass
+//     of the wave covers 64 / G heads; lane j of a group holds elements 16j .. 16j + 15 in
+//     registers (two 16-byte loads) — lanes with 16j >= D and groups past H_kv hold zeros;
+//   * the lane's amax (fmaxf: NaNs are ignored) meets the group's in log2 G butterfly steps of
+//     __shfl_xor (ds_bpermute: the crossbar, no LDS memory), after which every lane of the group
+//     holds the row's amax and forms the scale itself: amax / 127 (IEEE division), or 1 when
+//     amax < 2^-64 — such a row quantises to zeros, and the floor bounds 1 / scale and log2 scale
+//     for the decode kernels;
+//   * the lane quantises its 16 registers, q = clamp(round_half_away(x / scale), -127, 127)
+//     (append_q8's arithmetic), and stores one 16-byte chunk; lane 0 of the group stores the scale.
+// The input is read once; there is no LDS and no second pass.
+constexpr float kRowwiseFloor = 0x1p-64f;
+
+template <class E>
+__global__ __launch_bounds__(64 * kAppendWaves) void mfa_paged_append_rowwise_kernel(
+    PagedAppendRwParams pr) {
+  const PagedAppendParams& p = pr.a;
+  const int which = blockIdx.y;  // 0: key, 1: value
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const char* const src = (const char*)p.src[which];
+  char* const pool = (char*)p.pool[which];
+  float* const spool = pr.scales[which];
+  const int64_t sb = p.s_sb[which], sh = p.s_sh[which], ss = p.s_ss[which];  // bytes
+  const int G = 1 << pr.lg_group, hpp = 64 >> pr.lg_group;  // lanes per head, heads per pass
+  const int hl = lane >> pr.lg_group, ch = lane & (G - 1);
+  const bool chunk_live = 16 * ch < p.D;
+
+  for (int64_t row64 = (int64_t)blockIdx.x * kAppendWaves + wave; row64 < p.rows_total;
+       row64 += (int64_t)gridDim.x * kAppendWaves) {
+    const int row = (int)row64;
+    const int b = row / p.R, r = row - b * p.R;
+    const int len = ((append_i32_ptr)p.pg.seq_lens)[b];
+    const int n = p.new_lens ? min(max(((append_i32_ptr)p.new_lens)[b], 0), p.R) : p.R;
+    const int64_t t64 = (int64_t)len - n + r;  // any int32 length: no wrap
+    if (r >= n || t64 < 0 || t64 >= p.cap) continue;
+    const int t = (int)t64;  // < cap <= max_pages * page: the lookup stays in the table row
+    const int entry = ((append_i32_ptr)p.pg.block_table)[(int64_t)b * p.pg.max_pages +
+                                                         (t >> p.pg.lg_page)];
+    const int page = min(max(entry, 0), p.pg.num_pages - 1);
+    const int slot = t & ((1 << p.pg.lg_page) - 1);
+    char* const drow = pool + (int64_t)page * p.pg.page_bytes + (int64_t)slot * p.tok_bytes;
+    float* const srow_sc = spool + (int64_t)page * pr.sc_page + slot;
+    const char* const srow = src + b * sb + r * ss;
+    for (int h0 = 0; h0 < p.Hkv; h0 += hpp) {  // wave-uniform: every lane takes the shuffles
+      const int h = h0 + hl;
+      const bool live = chunk_live && h < p.Hkv;
+      u32x4 w0 = u32x4{0u, 0u, 0u, 0u}, w1 = w0;
+      if (live) {
+        const u32x4* s = (const u32x4*)(srow + h * sh + 32 * ch);
+        w0 = s[0];
+        w1 = s[1];
+      }
+      float a = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const uint32_t u = k < 4 ? w0[k & 3] : w1[k & 3];
+        a = fmaxf(a, fabsf(E::to_f32((uint16_t)u)));
+        a = fmaxf(a, fabsf(E::to_f32((uint16_t)(u >> 16))));
+      }
+      for (int o = 1; o < G; o <<= 1) a = fmaxf(a, __shfl_xor(a, o));
+      const float scale = a >= kRowwiseFloor ? a / 127.0f : 1.0f;
+      if (live) {
+        uint32_t q[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          const uint32_t u = k < 8 ? w0[k >> 1] : w1[(k >> 1) & 3];
+          const float x = E::to_f32((uint16_t)(u >> (16 * (k & 1))));
+          const float rq = roundf(x / scale);  // half away from zero
+          const int32_t i = !(rq == rq) ? 0 : (int32_t)fminf(fmaxf(rq, -127.f), 127.f);
+          q[k >> 2] |= (uint32_t)(uint8_t)(int8_t)i << (8 * (k & 3));
+        }
+        *(u32x4*)(drow + h * p.pg.head_bytes + 16 * ch) = u32x4{q[0], q[1], q[2], q[3]};
+        if (ch == 0) srow_sc[h * pr.sc_head] = scale;
+      }
+    }
+  }
+}
+
+hipError_t paged_append_rowwise_dispatch(const PagedAppendRwParams& p, int elem,
+                                         hipStream_t stream) {
+  // mfa_paged_append_kernel's grid: key and value halves of one launch.
+  const int64_t wgs = (p.a.rows_total + kAppendWaves - 1) / kAppendWaves;
+  const dim3 grid((unsigned)std::min<int64_t>(wgs, 32768), 2, 1), block(64 * kAppendWaves);
+  if (elem == P_FP16)
+    return launch(mfa_paged_append_rowwise_kernel<F16>, grid, block, 0, stream, p);
+  if (elem == P_BF16)
+    return launch(mfa_paged_append_rowwise_kernel<BF16>, grid, block, 0, stream, p);
+  return hipErrorNotSupported;
 }
 
 // The latent row and its rope key row of one new token, to slot t of the same page in two views

@@ -417,6 +417,28 @@ class PagedKVCache(ctypes.Structure):
         return c
 
 
+class PagedKVScales(ctypes.Structure):
+    """mfa_paged_kv_scales_t: one FP32 scale per (token slot, kv head) next to each pool of a
+    row-wise INT8 PagedKVCache (zero points 0; the cache's k_scale / v_scale are ignored)."""
+    _fields_ = [
+        ("k_scales", ctypes.c_void_p),
+        ("v_scales", ctypes.c_void_p),
+        ("strides", ctypes.c_int64 * 2),
+    ]
+
+    @classmethod
+    def make(cls, page_size, num_kv_heads, k_scales=None, v_scales=None, strides=None):
+        """Scale pools [num_pages, num_kv_heads, page_size] FP32 unless `strides` (page, kv head;
+        floats) says otherwise.  Tensors may be None for a plan query."""
+        s = cls()
+        s.k_scales, s.v_scales = _ptr(k_scales), _ptr(v_scales)
+        if strides is None:
+            strides = (num_kv_heads * page_size, page_size)
+        s.strides = (ctypes.c_int64 * 2)(*[int(x) for x in strides])
+        s._keep = (k_scales, v_scales)  # the struct holds raw device pointers
+        return s
+
+
 class PagedDecodeDescriptor(ctypes.Structure):
     _fields_ = [
         ("base", AttentionDescriptor),
@@ -637,6 +659,16 @@ _sig("mfa_paged_kv_append", ctypes.c_int,
       _P(PagedKVCache), _V])
 _sig("mfa_paged_kv_append_plan", ctypes.c_int,
      [_P(PagedAppendDescriptor), _P(PagedKVCache), _P(KernelPlan)])
+_sig("mfa_paged_kv_append_rowwise", ctypes.c_int,
+     [_P(PagedAppendDescriptor), _V, _V, _P(ctypes.c_int64), _P(ctypes.c_int64), _V,
+      _P(PagedKVCache), _P(PagedKVScales), _V])
+_sig("mfa_paged_kv_append_rowwise_plan", ctypes.c_int,
+     [_P(PagedAppendDescriptor), _P(PagedKVCache), _P(PagedKVScales), _P(KernelPlan)])
+_sig("mfa_paged_decode_forward_rowwise", ctypes.c_int,
+     [_P(PagedDecodeDescriptor), _V, _P(ctypes.c_int64), _P(PagedKVCache), _P(PagedKVScales), _V,
+      _V, _V])
+_sig("mfa_paged_decode_rowwise_plan", ctypes.c_int,
+     [_P(PagedDecodeDescriptor), _P(PagedKVCache), _P(PagedKVScales), _P(KernelPlan)])
 _sig("mfa_paged_mla_decode_forward", ctypes.c_int,
      [_P(PagedMLADecodeDescriptor), _V, _V, _V, _P(PagedLatentCache), _V, _V, _V])
 _sig("mfa_paged_mla_decode_plan", ctypes.c_int,
@@ -984,6 +1016,59 @@ def paged_kv_append_plan(desc: PagedAppendDescriptor,
     """mfa_paged_kv_append_plan: the kernel paged_kv_append launches (see multihead_plan);
     without a cache, a 16-bit cache of 256-key pages.  Needs no GPU."""
     return _paged_plan(lib.mfa_paged_kv_append_plan, desc, cache)
+
+
+def _ref(x):
+    return None if x is None else ctypes.byref(x)
+
+
+def paged_kv_append_rowwise(desc: PagedAppendDescriptor, key, value, cache: PagedKVCache,
+                            scales: PagedKVScales, new_lens=None, key_strides=None,
+                            value_strides=None, stream=None):
+    """mfa_paged_kv_append_rowwise: paged_kv_append into row-wise INT8 pools.  Every written
+    (row, kv head) is quantised with its own scale amax / 127 (1 below amax 2^-64, the row then
+    zeros), q = clamp(round_half_away(x / scale), -127, 127), and the scale goes to the slot's entry
+    of `scales`.  cache: INT8, zero points 0; its k_scale / v_scale are ignored."""
+    ks = _strides(key.stride() if key_strides is None and hasattr(key, "stride") else key_strides)
+    vs = _strides(value.stride() if value_strides is None and hasattr(value, "stride")
+                  else value_strides)
+    check(lib.mfa_paged_kv_append_rowwise(ctypes.byref(desc), _ptr(key), _ptr(value),
+                                          ks[0] if ks else None, vs[0] if vs else None,
+                                          _ptr(new_lens), ctypes.byref(cache), _ref(scales),
+                                          _stream(stream)))
+
+
+def paged_kv_append_rowwise_plan(desc: PagedAppendDescriptor, cache: Optional[PagedKVCache] = None,
+                                 scales: Optional[PagedKVScales] = None) -> list[dict]:
+    """mfa_paged_kv_append_rowwise_plan: the kernel paged_kv_append_rowwise launches; without a
+    cache, an INT8 cache of 256-key pages with dense scale pools.  Needs no GPU."""
+    out = KernelPlan()
+    check(lib.mfa_paged_kv_append_rowwise_plan(ctypes.byref(desc), _ref(cache), _ref(scales),
+                                               ctypes.byref(out)))
+    return out.as_list()
+
+
+def paged_decode_forward_rowwise(desc: PagedDecodeDescriptor, query, cache: PagedKVCache,
+                                 scales: PagedKVScales, output, logsumexp=None,
+                                 query_strides=None, stream=None):
+    """mfa_paged_decode_forward_rowwise: paged_decode_forward (masks, dead rows, splits, graph
+    capture) over row-wise INT8 pools: key j is scales.k_scales[j] * q_K[j], value j
+    scales.v_scales[j] * q_V[j].  No scale of a slot at or past a sequence's length is read."""
+    s = _strides(query_strides)
+    check(lib.mfa_paged_decode_forward_rowwise(ctypes.byref(desc), _ptr(query),
+                                               s[0] if s else None, ctypes.byref(cache),
+                                               _ref(scales), _ptr(output), _ptr(logsumexp),
+                                               _stream(stream)))
+
+
+def paged_decode_rowwise_plan(desc: PagedDecodeDescriptor, cache: Optional[PagedKVCache] = None,
+                              scales: Optional[PagedKVScales] = None) -> list[dict]:
+    """mfa_paged_decode_rowwise_plan: the kernels paged_decode_forward_rowwise launches; without a
+    cache, an INT8 cache of 256-key pages with dense scale pools.  Needs no GPU."""
+    out = KernelPlan()
+    check(lib.mfa_paged_decode_rowwise_plan(ctypes.byref(desc), _ref(cache), _ref(scales),
+                                            ctypes.byref(out)))
+    return out.as_list()
 
 
 def paged_mla_decode_forward(desc: PagedMLADecodeDescriptor, query, w_k, w_v,
