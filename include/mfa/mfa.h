@@ -516,8 +516,9 @@ typedef struct mfa_paged_kv_cache {
 
 /* Causal window (MFA_SPARSITY_CAUSAL_WINDOW, window_size = W; no reference counterpart): the
  * local-attention mask of a KV cache, served by mfa_paged_decode_forward (16-bit and INT8 pools,
- * both row forms) and its row-wise twin mfa_paged_decode_forward_rowwise, mfa_paged_prefill_forward, mfa_quantized_paged_prefill_forward and their three
- * *_plan functions.  Row q sits at key position t_q exactly as under MFA_SPARSITY_CAUSAL (decode:
+ * both row forms) and its row-wise twin mfa_paged_decode_forward_rowwise, mfa_paged_prefill_forward,
+ * mfa_quantized_paged_prefill_forward, mfa_paged_prefill_forward_rowwise and their *_plan
+ * functions.  Row q sits at key position t_q exactly as under MFA_SPARSITY_CAUSAL (decode:
  * len_b - R + q; prefill: len_b - n_b + q) and attends to keys j with t_q - W <= j <= t_q: W + 1
  * keys, the reference's row > col + window rule joined with the KV-cache causal rule.  W >= 2^30
  * is treated as 2^30, which is plain causal (bit for bit the MFA_SPARSITY_CAUSAL result); W = 0
@@ -640,9 +641,9 @@ typedef struct mfa_paged_kv_scales {
  * MFA_ERR_UNSUPPORTED: pools that are not INT8 (INT4 included), non-zero zero points, scale
  * strides or alignment outside the rules above.  batch_size == 0 or rows == 0 succeeds and
  * launches nothing.
- * Row-wise prefill is out of scope: mfa_quantized_paged_prefill_forward stays per-tensor.  A prompt
- * is prefilled from its 16-bit K/V (mfa_multihead_forward or a 16-bit paged cache) and then
- * appended row-wise. */
+ * The row-wise cache has the per-tensor cache's chain on one pair of structs, in stream order
+ * seq_lens += n -> mfa_paged_kv_append_rowwise -> mfa_paged_prefill_forward_rowwise (the prompt
+ * or chunk that was just appended) -> mfa_paged_decode_forward_rowwise (later tokens). */
 mfa_status_t mfa_paged_kv_append_rowwise(const mfa_paged_append_descriptor_t* desc,
                                          const void* key, const void* value,
                                          const int64_t* key_strides, const int64_t* value_strides,
@@ -756,6 +757,36 @@ mfa_status_t mfa_quantized_paged_prefill_forward(const mfa_paged_prefill_descrip
 mfa_status_t mfa_quantized_paged_prefill_plan(const mfa_paged_prefill_descriptor_t* desc,
                                               const mfa_paged_kv_cache_t* cache,
                                               mfa_kernel_plan_t* out);
+
+/* Paged prefill over row-wise INT8 pools (mfa_paged_kv_scales_t): the prompt step of the row-wise
+ * cache, between mfa_paged_kv_append_rowwise and mfa_paged_decode_forward_rowwise on one pair of
+ * structs.  From mfa_quantized_paged_prefill_forward it takes, unchanged: the descriptor, query /
+ * query_strides, new_lens, the lengths and their clamps; the three masks (NONE, CAUSAL,
+ * CAUSAL_WINDOW with the page-release contract); dead rows (exact zeros, L at its floor, never
+ * NaN), so every row of output and logsumexp is written; clamped page ids and table lookups; the
+ * grid of 128-row query blocks; no host read, no synchronisation, no workspace other than the
+ * scratch L; valid under stream capture.
+ * From mfa_paged_decode_forward_rowwise: the cache must be INT8 with zero points 0, its k_scale /
+ * v_scale are ignored, and the keys' values are k_scales[slot] * q_K, v_scales[slot] * q_V,
+ * applied per key inside the kernel (the MFMA operands are the exact integers q, so prefill and
+ * decode read one cache identically).  Scales of the keys read must be finite and positive.  No
+ * scale entry is fetched for a slot at or past len_b, for a page the table does not name for the
+ * keys read, or for a page wholly below the window's lo_b; a masked key contributes exactly 0.
+ * MFA_ERR_UNSUPPORTED, in the row-wise decode call's precedence (the cache struct's rules, then
+ * these, then the masks): pools that are not INT8 (INT4 included), non-zero zero points, scale
+ * strides or alignment outside mfa_paged_kv_scales_t's rules.  batch_size == 0 or rows == 0
+ * succeeds and launches nothing; the buffers and `scales` may then be null. */
+mfa_status_t mfa_paged_prefill_forward_rowwise(const mfa_paged_prefill_descriptor_t* desc,
+                                               const void* query, const int64_t* query_strides,
+                                               const int32_t* new_lens,
+                                               const mfa_paged_kv_cache_t* cache,
+                                               const mfa_paged_kv_scales_t* scales,
+                                               float* output, void* logsumexp, void* stream);
+/* The kernel that call launches; NULL cache / scales as for the row-wise append's plan. */
+mfa_status_t mfa_paged_prefill_rowwise_plan(const mfa_paged_prefill_descriptor_t* desc,
+                                            const mfa_paged_kv_cache_t* cache,
+                                            const mfa_paged_kv_scales_t* scales,
+                                            mfa_kernel_plan_t* out);
 
 /* ---------------------------------------------------------------------------------- */
 /* Paged MLA decode: absorbed attention over a paged latent cache.  (No reference      */

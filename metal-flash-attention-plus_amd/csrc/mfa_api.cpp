@@ -2250,12 +2250,15 @@ mfa_status_t paged_append(const mfa_paged_append_descriptor_t* desc, const void*
 // (mfa_paged_prefill_forward): 16-bit pools only.  allow_i8 = true
 // (mfa_quantized_paged_prefill_forward): INT8 pools as well, widened on load
 // (attention_prefill_paged_kv8.hip) with the decode call's folded scales; 16-bit pools take the
-// same launch either way.
+// same launch either way.  rw (mfa_paged_prefill_forward_rowwise): row-wise INT8 pools, the
+// scales applied per key in the kernel (attention_prefill_paged_rw8.hip).
 mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const void* query,
                            const int64_t* query_strides, const int32_t* new_lens,
                            const mfa_paged_kv_cache_t* cache, float* output, void* logsumexp,
-                           hipStream_t stream, bool allow_i8) {
-  const char* const what = allow_i8 ? "quantized paged prefill" : "paged prefill";
+                           hipStream_t stream, bool allow_i8, RowwiseArg* rw = nullptr) {
+  const char* const what = rw         ? "row-wise paged prefill"
+                           : allow_i8 ? "quantized paged prefill"
+                                      : "paged prefill";
   return paged_kv_forward(
       what, desc, query, query_strides, cache, output, logsumexp, stream, allow_i8,
       [&](int64_t B, int64_t H, int64_t, int64_t R) -> mfa_status_t {
@@ -2267,12 +2270,14 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
       },
       [&](const mfa::FwdParams& p, const PagedCacheView& cv, int elem) -> mfa_status_t {
         const hipError_t e =
-            cv.i8 ? mfa::fwd_prefill_paged_kv8_dispatch(p, cv.pg, new_lens, elem, stream)
-                  : mfa::fwd_prefill_paged_dispatch(p, cv.pg, new_lens, elem, stream);
+            rw      ? mfa::fwd_prefill_paged_rw8_dispatch(p, cv.pg, rw->sc, new_lens, elem, stream)
+            : cv.i8 ? mfa::fwd_prefill_paged_kv8_dispatch(p, cv.pg, new_lens, elem, stream)
+                    : mfa::fwd_prefill_paged_dispatch(p, cv.pg, new_lens, elem, stream);
         if (e == hipErrorNotSupported)
           return fail(MFA_ERR_UNSUPPORTED, "%s: no kernel for this call", what);
         return hip_status(e, "mfa_fwd (paged prefill) launch");
-      });
+      },
+      rw);
 }
 
 // -----------------------------------------------------------------------------------------
@@ -2811,6 +2816,28 @@ extern "C" mfa_status_t mfa_quantized_paged_prefill_plan(
                       return paged_prefill(desc, (const void*)kPlanDummy, nullptr, nullptr, &c,
                                            (float*)kPlanDummy, nullptr, nullptr, true);
                     });
+}
+
+extern "C" mfa_status_t mfa_paged_prefill_forward_rowwise(
+    const mfa_paged_prefill_descriptor_t* desc, const void* query, const int64_t* query_strides,
+    const int32_t* new_lens, const mfa_paged_kv_cache_t* cache,
+    const mfa_paged_kv_scales_t* scales, float* output, void* logsumexp, void* stream) {
+  RowwiseArg rw{scales, {}};
+  return paged_prefill(desc, query, query_strides, new_lens, cache, output, logsumexp,
+                       (hipStream_t)stream, true, &rw);
+}
+
+extern "C" mfa_status_t mfa_paged_prefill_rowwise_plan(const mfa_paged_prefill_descriptor_t* desc,
+                                                       const mfa_paged_kv_cache_t* cache,
+                                                       const mfa_paged_kv_scales_t* scales,
+                                                       mfa_kernel_plan_t* out) {
+  if (!desc || !out) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  return paged_plan(*desc, MFA_PRECISION_INT8, cache, out, [&](const mfa_paged_kv_cache_t& c) {
+    const mfa_paged_kv_scales_t s = plan_scales(scales, c, desc->num_kv_heads);
+    RowwiseArg rw{&s, {}};
+    return paged_prefill(desc, (const void*)kPlanDummy, nullptr, nullptr, &c, (float*)kPlanDummy,
+                         nullptr, nullptr, true, &rw);
+  });
 }
 
 extern "C" mfa_status_t mfa_paged_mla_decode_forward(const mfa_paged_mla_descriptor_t* desc,

@@ -91,6 +91,11 @@ hipError_t fwd_prefill_paged_dispatch(const FwdParams& p, const PagedKv& pg,
 // p.k.ss in bytes, p.k.zp / p.v.zp the zero points, the scales folded into p.c_log2 and p.o_mul.
 hipError_t fwd_prefill_paged_kv8_dispatch(const FwdParams& p, const PagedKv& pg,
                                           const int32_t* new_lens, int elem, hipStream_t stream);
+// ... over row-wise INT8 pools (attention_prefill_paged_rw8.hip): a scale per (key, kv head) in
+// `sc`, applied in the kernel; p.k.zp = p.v.zp = 0, p.c_log2 without a K scale, p.o_mul = 1.
+hipError_t fwd_prefill_paged_rw8_dispatch(const FwdParams& p, const PagedKv& pg,
+                                          const PagedKvScales& sc, const int32_t* new_lens,
+                                          int elem, hipStream_t stream);
 // The write side of that cache (paged_append.hip): one launch scatters the new key and value
 // rows (16-bit, type `elem`) into 16-bit pools of the same type or, with i8, quantises them into
 // per-tensor INT8 pools.  operands = 2: key and value; 1: index 0 of each pair alone (the latent

@@ -140,6 +140,15 @@ struct PagedPrefillParams {
   const int32_t* new_lens;     // [B] rows of each sequence (clamped to [0, f.R]); NULL: f.R
 };
 
+// ... over row-wise INT8 pools (attention_prefill_paged_rw8.hip): f.k.zp = f.v.zp = 0, f.c_log2
+// carries no K scale and f.o_mul is 1.
+struct PagedRwPrefillParams {
+  FwdParams f;
+  PagedKv pg;
+  const int32_t* new_lens;
+  PagedKvScales sc;
+};
+
 // Append to a paged cache (paged_append.hip): index 0 of each pair is the key, 1 the value.
 struct PagedAppendParams {
   const void* src[2];          // new rows [B, H_kv, R, D], 16-bit, d contiguous

@@ -31,6 +31,18 @@ __device__ __forceinline__ int64_t prefill_segment(const PagedKv& pg, int page, 
   return (int64_t)id * pg.page_bytes + (int64_t)(t & ((1 << pg.lg_page) - 1)) * ssb;
 }
 
+// The same segment in a row-wise scale pool (PagedKvScales: one float per token slot, `page`
+// floats between pages): the offset in floats from a head's first scale, and the bytes a load may
+// touch under prefill_segment's rule — no scale of a slot at or past `len`, nor of another page.
+__device__ __forceinline__ int64_t prefill_scale_segment(const PagedKv& pg, int64_t page_stride,
+                                                         int page, int t, int len, int* bytes) {
+  const int pend = ((t >> pg.lg_page) + 1) << pg.lg_page;
+  const int rows = min(min(len, pend) - t, 32);
+  *bytes = rows > 0 ? rows * 4 : 0;
+  const int id = min(max(page, 0), pg.num_pages - 1);
+  return (int64_t)id * page_stride + (t & ((1 << pg.lg_page) - 1));
+}
+
 // The result of a row with no visible key: zeros and L = -FLT_MAX (-inf once rounded to FP16),
 // in store_o_l's lane layout.
 template <int DP>

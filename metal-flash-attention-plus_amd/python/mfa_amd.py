@@ -669,6 +669,11 @@ _sig("mfa_paged_decode_forward_rowwise", ctypes.c_int,
       _V, _V])
 _sig("mfa_paged_decode_rowwise_plan", ctypes.c_int,
      [_P(PagedDecodeDescriptor), _P(PagedKVCache), _P(PagedKVScales), _P(KernelPlan)])
+_sig("mfa_paged_prefill_forward_rowwise", ctypes.c_int,
+     [_P(PagedPrefillDescriptor), _V, _P(ctypes.c_int64), _V, _P(PagedKVCache), _P(PagedKVScales),
+      _V, _V, _V])
+_sig("mfa_paged_prefill_rowwise_plan", ctypes.c_int,
+     [_P(PagedPrefillDescriptor), _P(PagedKVCache), _P(PagedKVScales), _P(KernelPlan)])
 _sig("mfa_paged_mla_decode_forward", ctypes.c_int,
      [_P(PagedMLADecodeDescriptor), _V, _V, _V, _P(PagedLatentCache), _V, _V, _V])
 _sig("mfa_paged_mla_decode_plan", ctypes.c_int,
@@ -1068,6 +1073,30 @@ def paged_decode_rowwise_plan(desc: PagedDecodeDescriptor, cache: Optional[Paged
     out = KernelPlan()
     check(lib.mfa_paged_decode_rowwise_plan(ctypes.byref(desc), _ref(cache), _ref(scales),
                                             ctypes.byref(out)))
+    return out.as_list()
+
+
+def paged_prefill_forward_rowwise(desc: PagedPrefillDescriptor, query, cache: PagedKVCache,
+                                  scales: PagedKVScales, output, new_lens=None, logsumexp=None,
+                                  query_strides=None, stream=None):
+    """mfa_paged_prefill_forward_rowwise: quantized_paged_prefill_forward (lengths, new_lens,
+    masks, dead rows, graph capture) over row-wise INT8 pools, the per-key scales applied inside
+    the kernel: the step between paged_kv_append_rowwise and paged_decode_forward_rowwise on one
+    cache and one `scales`.  No scale of a slot at or past a sequence's length is read."""
+    s = _strides(query_strides)
+    check(lib.mfa_paged_prefill_forward_rowwise(ctypes.byref(desc), _ptr(query),
+                                                s[0] if s else None, _ptr(new_lens),
+                                                ctypes.byref(cache), _ref(scales), _ptr(output),
+                                                _ptr(logsumexp), _stream(stream)))
+
+
+def paged_prefill_rowwise_plan(desc: PagedPrefillDescriptor, cache: Optional[PagedKVCache] = None,
+                               scales: Optional[PagedKVScales] = None) -> list[dict]:
+    """mfa_paged_prefill_rowwise_plan: the kernel paged_prefill_forward_rowwise launches; without
+    a cache, an INT8 cache of 256-key pages with dense scale pools.  Needs no GPU."""
+    out = KernelPlan()
+    check(lib.mfa_paged_prefill_rowwise_plan(ctypes.byref(desc), _ref(cache), _ref(scales),
+                                             ctypes.byref(out)))
     return out.as_list()
 
 
