@@ -1047,6 +1047,95 @@ mfa_status_t mfa_paged_mla_rope_prefill_plan(const mfa_paged_mla_descriptor_t* d
                                              const mfa_paged_rope_cache_t* rope,
                                              mfa_kernel_plan_t* out);
 
+/* ---------------------------------------------------------------------------------- */
+/* Paged MLA over a row-wise INT8 latent cache: one byte per latent element and one    */
+/* FP32 scale per token, computed on the device as the row is written.  (No reference   */
+/* counterpart.)  The rope part, where there is one, stays 16-bit.                      */
+
+/* The per-token scales of an INT8 latent cache.  It sits next to a mfa_paged_latent_cache_t whose
+ * `precision` is MFA_PRECISION_INT8 and is indexed by that cache's page ids and slots.  Such a
+ * cache keeps the struct's rules with byte elements: strides >= 0 and multiples of 16 bytes,
+ * token stride >= latent bytes and below 2^24 bytes, the pool 16-byte aligned.  The rope part
+ * stays in the descriptor's 16-bit `precision` and goes through mfa_paged_rope_cache_t; each
+ * struct has strides in its own elements, so fused rows [latent bytes | 64 rope elements] are the
+ * latent cache with a token stride of latent + 128 and the rope cache with one of latent / 2 + 64
+ * (latent 512: 640 and 320).  Rules of this struct: page_stride >= page_size and a multiple of 4
+ * floats, the pool 16-byte aligned; else MFA_ERR_UNSUPPORTED. */
+typedef struct mfa_paged_latent_scales {
+  const float* scales;   /* device; page p, slot t at p*page_stride + t */
+  int64_t page_stride;   /* floats; >= page_size, a multiple of 4; pool 16-byte aligned */
+} mfa_paged_latent_scales_t;
+
+/* mfa_paged_latent_rope_append into an INT8 latent cache: that call's contract — addressing,
+ * new_lens raggedness, the never-written guarantees, one launch, valid under stream capture —
+ * with the latent row quantised as it is written.  `desc->precision` is the type of `latent` and
+ * `k_rope` (and of the rope pool); cache->precision must be MFA_PRECISION_INT8.  k_rope and rope
+ * are NULL together for a cache without a rope part; one given and the other NULL is
+ * MFA_ERR_INVALID_ARGUMENT where the buffers are checked.  Per written row the quantiser is
+ * mfa_paged_kv_append_rowwise's on one "head" of kv_latent_dim elements:
+ *   a = max_d |x_d| (NaNs ignored);  scale = a >= 2^-64 ? a / 127.0f : 1.0f;
+ *   q_d = clamp(round_half_away(x_d / scale), -127, 127), a NaN element gives 0.
+ * The scale goes to the slot's entry of the scale pool; no other scale entry is written.  Rope
+ * rows are copied with their bits unchanged.  The structs are checked in the rope append's
+ * order, the scales struct with the cache struct; a latent cache that is not INT8, and a scale
+ * stride or alignment outside the rules: MFA_ERR_UNSUPPORTED; NULL scales or scales->scales:
+ * MFA_ERR_INVALID_ARGUMENT where the other buffers are checked. */
+mfa_status_t mfa_paged_latent_append_rowwise(const mfa_paged_latent_append_descriptor_t* desc,
+                                             const void* latent, const int64_t* latent_strides,
+                                             const void* k_rope, const int64_t* k_rope_strides,
+                                             const int32_t* new_lens,
+                                             const mfa_paged_latent_cache_t* cache,
+                                             const mfa_paged_latent_scales_t* scales,
+                                             const mfa_paged_rope_cache_t* rope, void* stream);
+/* The kernel that call launches (see mfa_multihead_plan).  with_rope != 0 plans the call with a
+ * rope part (rope == NULL: a separate dense rope pool), with_rope == 0 the call without one (rope
+ * must be NULL).  cache == NULL plans an INT8 cache of 256-key pages, scales == NULL a dense
+ * scale pool over the cache's pages; NULL pointers inside a struct plan aligned buffers. */
+mfa_status_t mfa_paged_latent_append_rowwise_plan(const mfa_paged_latent_append_descriptor_t* desc,
+                                                  const mfa_paged_latent_cache_t* cache,
+                                                  const mfa_paged_latent_scales_t* scales,
+                                                  const mfa_paged_rope_cache_t* rope,
+                                                  int32_t with_rope, mfa_kernel_plan_t* out);
+
+/* The decode step over that cache.  q_rope and rope are NULL together: the call is then
+ * mfa_paged_mla_decode_forward's contract; otherwise mfa_paged_mla_rope_decode_forward's — both
+ * masks in the KV-cache convention, rows with no visible key, clamps, limits, three launches,
+ * scratch, and stream / graph behaviour (seq_lens += n, mfa_paged_latent_append_rowwise and this
+ * call replay as one graph after one warm-up call).  `desc->precision` is the 16-bit type E of
+ * query, weights, q_rope and the rope pool; cache->precision must be MFA_PRECISION_INT8.
+ * The only difference is the value of key j's latent row:
+ *   c_j[d] = E(scales[j] * (float)q_j[d]),
+ * one FP32 product rounded once, to nearest even, to E.  So the call returns, bit for bit, what
+ * the 16-bit call returns on a pool that holds those rounded rows.  Scales of the keys read must
+ * be finite and positive.
+ * Safety, added to the 16-bit calls' rules: no byte and no scale entry of a slot at or past len_b
+ * is fetched, nor any of a page the table does not name for the keys read; a row at or past len_b
+ * is zeros whatever its scale entry holds, NaN included.
+ * Status: the rope decode call's precedence, the scales struct checked with the cache struct.  A
+ * latent cache that is not INT8, and a scale stride or alignment outside the rules:
+ * MFA_ERR_UNSUPPORTED.  NULL scales or scales->scales, and q_rope or rope given singly:
+ * MFA_ERR_INVALID_ARGUMENT where the other buffers are checked.  The 16-bit MLA calls keep
+ * returning MFA_ERR_UNSUPPORTED for an INT8 latent cache.
+ * Three launches: the query projection, mfa_mla_latent_paged_rw8_kernel (the bytes are widened,
+ * scaled and rounded on their way into the LDS tile the 16-bit kernel fills), and the unchanged
+ * merge that applies W_v.
+ * Out of scope: prefill over the INT8 latent; the dense mfa_mla_forward_absorbed; FP8 or INT4
+ * latents; a quantised rope part; block-wise scales within a row. */
+mfa_status_t mfa_paged_mla_decode_forward_rowwise(const mfa_paged_mla_descriptor_t* desc,
+                                                  const void* query, const void* q_rope,
+                                                  const void* w_k, const void* w_v,
+                                                  const mfa_paged_latent_cache_t* cache,
+                                                  const mfa_paged_latent_scales_t* scales,
+                                                  const mfa_paged_rope_cache_t* rope,
+                                                  float* output, void* logsumexp, void* stream);
+/* The kernels that call launches (see mfa_paged_latent_append_rowwise_plan for with_rope and
+ * NULL structs). */
+mfa_status_t mfa_paged_mla_decode_rowwise_plan(const mfa_paged_mla_descriptor_t* desc,
+                                               const mfa_paged_latent_cache_t* cache,
+                                               const mfa_paged_latent_scales_t* scales,
+                                               const mfa_paged_rope_cache_t* rope,
+                                               int32_t with_rope, mfa_kernel_plan_t* out);
+
 /* GPU runtime quantization (GEMMQuantization.swift:305-623 semantics, bit-exact; the
  * reference does this on the CPU in QuantizedTensor.from, :720-860).
  * input: device tensor of `count` elements in `input_precision` (FP32/FP16/BF16), viewed as

@@ -1193,6 +1193,19 @@ hipError_t mla_latent_dispatch(const LatentParams& p, int elem, int lat, hipStre
   return hipErrorNotSupported;
 }
 
+hipError_t mla_latent_merge_dispatch(const LatentParams& p, int elem, int lat, hipStream_t stream) {
+  const dim3 grid(p.B * p.R), block(MNT);
+  if (lat == 512 && elem == P_FP16)
+    return launch(mfa_mla_latent_merge_kernel<F16, 512, 1>, grid, block, 0, stream, p);
+  if (lat == 512 && elem == P_BF16)
+    return launch(mfa_mla_latent_merge_kernel<BF16, 512, 1>, grid, block, 0, stream, p);
+  if (lat == 256 && elem == P_FP16)
+    return launch(mfa_mla_latent_merge_kernel<F16, 256, 1>, grid, block, 0, stream, p);
+  if (lat == 256 && elem == P_BF16)
+    return launch(mfa_mla_latent_merge_kernel<BF16, 256, 1>, grid, block, 0, stream, p);
+  return hipErrorNotSupported;
+}
+
 hipError_t mla_latent_paged_dispatch(const LatentPagedParams& p, int elem, int lat,
                                      hipStream_t stream) {
   if (lat == 512 && elem == P_FP16) return launch_latent_paged<F16, 512>(p, stream);

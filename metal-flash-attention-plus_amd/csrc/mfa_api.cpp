@@ -2289,7 +2289,7 @@ mfa_status_t paged_prefill(const mfa_paged_prefill_descriptor_t* desc, const voi
 // head stride and token slots of Lat elements (stride index 2 in a message is the token stride).
 mfa_status_t paged_latent_view(const char* what, const mfa_paged_latent_cache_t& c, int64_t B,
                                int64_t Lat, uint32_t max_seq_len, int prec16, const char* whose,
-                               PagedCacheView* v) {
+                               PagedCacheView* v, bool allow_i8 = false) {
   mfa_paged_kv_cache_t kv;
   memset(&kv, 0, sizeof(kv));
   kv.k_pool = kv.v_pool = c.pool;
@@ -2302,8 +2302,38 @@ mfa_status_t paged_latent_view(const char* what, const mfa_paged_latent_cache_t&
   kv.page_size = c.page_size;
   kv.max_pages_per_seq = c.max_pages_per_seq;
   kv.num_pages = c.num_pages;
-  return paged_cache_view(what, kv, B, Lat, max_seq_len, prec16, whose, false, v, Lat);
+  return paged_cache_view(what, kv, B, Lat, max_seq_len, prec16, whose, allow_i8, v, Lat);
 }
+
+// Row-wise INT8 latent pools (the two *_rowwise MLA calls): the cache must be INT8, and the scales
+// struct, where there is one, keeps its stride rule.  Applied right after the cache view; `scales`
+// may still be null here (an empty call may pass none).
+mfa_status_t paged_latent_rowwise_view(const char* what, const mfa_paged_latent_cache_t& c,
+                                       const PagedCacheView& v,
+                                       const mfa_paged_latent_scales_t* scales) {
+  if (!v.i8)
+    return fail(MFA_ERR_UNSUPPORTED, "%s: row-wise scales need an INT8 latent pool (precision %d)",
+                what, v.cprec);
+  if (!scales) return MFA_SUCCESS;
+  if (scales->page_stride < (int64_t)c.page_size || scales->page_stride % 4 != 0)
+    return fail(MFA_ERR_UNSUPPORTED,
+                "%s: scale page stride %lld (a multiple of 4 floats, at least the page size)", what,
+                (long long)scales->page_stride);
+  return MFA_SUCCESS;
+}
+
+// ... and after the cache's buffers (their null check covers the scale pool): its alignment.
+mfa_status_t paged_latent_rowwise_buffers(const char* what,
+                                          const mfa_paged_latent_scales_t* scales) {
+  if (!aligned16(scales->scales))
+    return fail(MFA_ERR_UNSUPPORTED, "%s: the scale pool must be 16-byte aligned", what);
+  return MFA_SUCCESS;
+}
+
+// The scales argument of a row-wise MLA entry point (null: the 16-bit call).
+struct LatentRowwiseArg {
+  const mfa_paged_latent_scales_t* scales;
+};
 
 // paged_cache_buffers for the one-pool cache.
 mfa_status_t paged_latent_buffers(const char* what, const mfa_paged_latent_cache_t& c,
@@ -2348,17 +2378,17 @@ mfa_paged_rope_cache_t plan_rope(const mfa_paged_rope_cache_t* rope,
   return r;
 }
 
-// paged_plan for the one-pool cache: without one, a dense 16-bit cache of 256-key pages.
+// paged_plan for the one-pool cache: without one, a dense 16-bit (i8: INT8) cache of 256-key pages.
 template <class Desc, class Run>
 mfa_status_t paged_latent_plan(const Desc& d, const mfa_paged_latent_cache_t* cache,
-                               mfa_kernel_plan_t* out, Run run) {
+                               mfa_kernel_plan_t* out, Run run, bool i8 = false) {
   memset(out, 0, sizeof(*out));
   mfa_paged_latent_cache_t c;
   if (cache) {
     c = *cache;
   } else {
     memset(&c, 0, sizeof(c));
-    c.precision = d.precision;
+    c.precision = i8 ? (int32_t)MFA_PRECISION_INT8 : d.precision;
     c.page_size = 256;
     c.max_pages_per_seq = (d.max_seq_len + 255) / 256;
     c.num_pages = std::max<uint32_t>(1, c.max_pages_per_seq * d.batch_size);
@@ -2378,11 +2408,12 @@ mfa_status_t paged_latent_plan(const Desc& d, const mfa_paged_latent_cache_t* ca
 // for every shape, and its B · ceil(H·R / 32) workgroups follow from B · H · R < 2^31.
 // with_rope (the two rope calls, decode and prefill): a given rope struct is checked behind the
 // cache struct (a null one is the buffers' fault, later), and the scale falls back to the joint
-// width.
+// width.  rw (the row-wise decode call): an INT8 pool, the scales struct checked with the cache.
 mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* desc,
                             const mfa_paged_latent_cache_t* cache, bool prefill,
                             PagedCacheView* cv, float* scale_out, bool with_rope = false,
-                            const mfa_paged_rope_cache_t* rope = nullptr) {
+                            const mfa_paged_rope_cache_t* rope = nullptr,
+                            const LatentRowwiseArg* rw = nullptr) {
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const mfa_attention_descriptor_t& base = desc->base;
   const int64_t B = desc->batch_size, H = desc->num_heads, R = desc->rows;
@@ -2396,9 +2427,11 @@ mfa_status_t paged_mla_view(const char* what, const mfa_paged_mla_descriptor_t* 
   if (Lat != 256 && Lat != 512)
     return fail(MFA_ERR_UNSUPPORTED, "%s: latent dimension %lld (256 or 512)", what,
                 (long long)Lat);
-  mfa_status_t st =
-      paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "descriptor's", cv);
+  mfa_status_t st = paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec,
+                                      "descriptor's", cv, rw != nullptr);
   if (st != MFA_SUCCESS) return st;
+  if (rw && (st = paged_latent_rowwise_view(what, *cache, *cv, rw->scales)) != MFA_SUCCESS)
+    return st;
   if (with_rope && rope && (st = paged_rope_view(what, *rope)) != MFA_SUCCESS) return st;
   if (D % 8 != 0 || D > 256)
     return fail(MFA_ERR_UNSUPPORTED, "%s: head dimension %lld (a multiple of 8, at most 256)",
@@ -2427,13 +2460,20 @@ mfa_status_t paged_mla_buffers(const char* what, const mfa_paged_latent_cache_t&
                                const void* query, const void* w_k, const void* w_v,
                                const void* output, bool with_rope = false,
                                const void* q_rope = nullptr,
-                               const mfa_paged_rope_cache_t* rope = nullptr) {
-  const bool own = query && w_k && w_v && output;
-  const mfa_status_t st =
-      with_rope ? paged_latent_buffers(what, cache, "query, q_rope, w_k, w_v, output, the rope pool",
+                               const mfa_paged_rope_cache_t* rope = nullptr,
+                               const LatentRowwiseArg* rw = nullptr) {
+  const bool own = query && w_k && w_v && output && (!rw || (rw->scales && rw->scales->scales));
+  mfa_status_t st =
+      with_rope ? paged_latent_buffers(what, cache,
+                                       rw ? "query, q_rope, w_k, w_v, output, the scale and rope pools"
+                                          : "query, q_rope, w_k, w_v, output, the rope pool",
                                        own && q_rope && rope && rope->pool)
-                : paged_latent_buffers(what, cache, "query, w_k, w_v, output", own);
+                : paged_latent_buffers(what, cache,
+                                       rw ? "query, w_k, w_v, output, the scale pool"
+                                          : "query, w_k, w_v, output",
+                                       own);
   if (st != MFA_SUCCESS) return st;
+  if (rw && (st = paged_latent_rowwise_buffers(what, rw->scales)) != MFA_SUCCESS) return st;
   if (!aligned16(query) || !aligned16(w_k) || !aligned16(w_v))
     return fail(MFA_ERR_UNSUPPORTED, "%s: query and weights must be 16-byte aligned", what);
   if (with_rope && (!aligned16(q_rope) || !aligned16(rope->pool)))
@@ -2448,24 +2488,29 @@ mfa_status_t paged_mla_buffers(const char* what, const mfa_paged_latent_cache_t&
 // with_rope (mfa_paged_mla_rope_decode_forward): the same route and scratch with
 // mfa_mla_latent_paged_rope_kernel in the latent kernel's place — the rope pool as a second view
 // of the cache's pages, q_rope [B, H, R, 64] next to Q̃.
+// rw (mfa_paged_mla_decode_forward_rowwise): the same again over an INT8 pool with per-token
+// scales, mfa_mla_latent_paged_rw8_kernel with or without the rope part.
 mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void* query,
                               const void* w_k, const void* w_v,
                               const mfa_paged_latent_cache_t* cache, float* output,
                               void* logsumexp, hipStream_t stream, bool with_rope = false,
                               const void* q_rope = nullptr,
-                              const mfa_paged_rope_cache_t* rope = nullptr) {
-  const char* const what = with_rope ? "paged MLA rope decode" : "paged MLA decode";
+                              const mfa_paged_rope_cache_t* rope = nullptr,
+                              const LatentRowwiseArg* rw = nullptr) {
+  const char* const what = rw          ? "paged MLA row-wise decode"
+                           : with_rope ? "paged MLA rope decode"
+                                       : "paged MLA decode";
   PagedCacheView cv;
   float scale = 0.f;
-  mfa_status_t st = paged_mla_view(what, desc, cache, false, &cv, &scale, with_rope, rope);
+  mfa_status_t st = paged_mla_view(what, desc, cache, false, &cv, &scale, with_rope, rope, rw);
   if (st != MFA_SUCCESS) return st;
   const mfa_attention_descriptor_t& base = desc->base;
   const int64_t B = desc->batch_size, H = desc->num_heads, R = desc->rows;
   const int64_t D = desc->head_dim, Lat = desc->kv_latent_dim;
   const int prec = desc->precision;
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to compute; the buffers may be null
-  if ((st = paged_mla_buffers(what, *cache, query, w_k, w_v, output, with_rope, q_rope, rope)) !=
-      MFA_SUCCESS)
+  if ((st = paged_mla_buffers(what, *cache, query, w_k, w_v, output, with_rope, q_rope, rope,
+                              rw)) != MFA_SUCCESS)
     return st;
 
   const AbsorbedLayout al = absorbed_layout((int)B, (int)H, (int)R, (int)cv.cap, (int)Lat);
@@ -2502,15 +2547,26 @@ mfa_status_t paged_mla_decode(const mfa_paged_mla_descriptor_t* desc, const void
   p.pg = cv.pg;
   p.tok_bytes = cache->strides[1] * cv.es;
   hipError_t e;
-  if (with_rope) {
+  if (with_rope || rw) {
     mfa::LatentPagedRopeParams pr;
     memset(&pr, 0, sizeof(pr));
     pr.c = p;
-    pr.rope = rope->pool;
-    pr.rope_page_bytes = rope->strides[0] * cv.es;
-    pr.rope_tok_bytes = rope->strides[1] * cv.es;
-    pr.q_rope = q_rope;
-    e = mfa::mla_latent_paged_rope_dispatch(pr, elem_of(prec), (int)Lat, stream);
+    if (with_rope) {  // the rope part is 16-bit beside an INT8 latent too
+      pr.rope = rope->pool;
+      pr.rope_page_bytes = rope->strides[0] * 2;
+      pr.rope_tok_bytes = rope->strides[1] * 2;
+      pr.q_rope = q_rope;
+    }
+    if (rw) {
+      mfa::LatentPagedRw8Params pw;
+      memset(&pw, 0, sizeof(pw));
+      pw.r = pr;
+      pw.scales = rw->scales->scales;
+      pw.sc_page = rw->scales->page_stride;
+      e = mfa::mla_latent_paged_rw8_dispatch(pw, with_rope, elem_of(prec), (int)Lat, stream);
+    } else {
+      e = mfa::mla_latent_paged_rope_dispatch(pr, elem_of(prec), (int)Lat, stream);
+    }
   } else {
     e = mfa::mla_latent_paged_dispatch(p, elem_of(prec), (int)Lat, stream);
   }
@@ -2598,14 +2654,19 @@ mfa_status_t paged_mla_prefill(const mfa_paged_mla_descriptor_t* desc, const voi
 // elements, no head stride.
 // with_rope (mfa_paged_latent_rope_append): the rope key rows k_rope [B, R, 64] go with the latent
 // rows, to the same slots of the rope view, in one launch of a kernel with two operand widths.
+// rw (mfa_paged_latent_append_rowwise): an INT8 pool, every written row quantised with a scale of
+// its own in the scale pool; with or without the rope rows, one launch of a kernel of its own.
 mfa_status_t paged_latent_append(const mfa_paged_latent_append_descriptor_t* desc,
                                  const void* latent, const int64_t* latent_strides,
                                  const int32_t* new_lens, const mfa_paged_latent_cache_t* cache,
                                  hipStream_t stream, bool with_rope = false,
                                  const void* k_rope = nullptr,
                                  const int64_t* k_rope_strides = nullptr,
-                                 const mfa_paged_rope_cache_t* rope = nullptr) {
-  const char* const what = with_rope ? "paged latent rope append" : "paged latent append";
+                                 const mfa_paged_rope_cache_t* rope = nullptr,
+                                 const LatentRowwiseArg* rw = nullptr) {
+  const char* const what = rw          ? "paged latent row-wise append"
+                           : with_rope ? "paged latent rope append"
+                                       : "paged latent append";
   if (!desc || !cache) return fail(MFA_ERR_INVALID_ARGUMENT, "%s: null descriptor or cache", what);
   const int64_t B = desc->batch_size, R = desc->rows, Lat = desc->kv_latent_dim;
   if (Lat == 0 || desc->max_seq_len == 0 || cache->max_pages_per_seq == 0 || cache->num_pages == 0)
@@ -2617,17 +2678,23 @@ mfa_status_t paged_latent_append(const mfa_paged_latent_append_descriptor_t* des
     return fail(MFA_ERR_UNSUPPORTED, "%s: latent dimension %lld (256 or 512)", what,
                 (long long)Lat);
   PagedCacheView cv;
-  mfa_status_t st =
-      paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "input's", &cv);
+  mfa_status_t st = paged_latent_view(what, *cache, B, Lat, desc->max_seq_len, prec, "input's",
+                                      &cv, rw != nullptr);
   if (st != MFA_SUCCESS) return st;
+  if (rw && (st = paged_latent_rowwise_view(what, *cache, cv, rw->scales)) != MFA_SUCCESS)
+    return st;
   if (with_rope && rope && (st = paged_rope_view(what, *rope)) != MFA_SUCCESS) return st;
   if (B * R >= ((int64_t)1 << 31))
     return fail(MFA_ERR_UNSUPPORTED, "%s: too many rows", what);
   if (B == 0 || R == 0) return MFA_SUCCESS;  // nothing to write; the buffers may be null
-  st = with_rope ? paged_latent_buffers(what, *cache, "latent, k_rope, the rope pool",
-                                        latent && k_rope && rope && rope->pool)
-                 : paged_latent_buffers(what, *cache, "latent", latent != nullptr);
+  const bool own = latent && (!rw || (rw->scales && rw->scales->scales));
+  st = with_rope ? paged_latent_buffers(what, *cache,
+                                        rw ? "latent, k_rope, the scale and rope pools"
+                                           : "latent, k_rope, the rope pool",
+                                        own && k_rope && rope && rope->pool)
+                 : paged_latent_buffers(what, *cache, rw ? "latent, the scale pool" : "latent", own);
   if (st != MFA_SUCCESS) return st;
+  if (rw && (st = paged_latent_rowwise_buffers(what, rw->scales)) != MFA_SUCCESS) return st;
   if (with_rope && !aligned16(rope->pool))
     return fail(MFA_ERR_UNSUPPORTED, "%s: the rope pool must be 16-byte aligned", what);
 
@@ -2639,29 +2706,43 @@ mfa_status_t paged_latent_append(const mfa_paged_latent_append_descriptor_t* des
     if (s[j] < 0 || s[j] % 8 != 0)
       return fail(MFA_ERR_UNSUPPORTED, "%s: latent stride %d is not a multiple of 8 elements",
                   what, j);
-  if (with_rope) {
+  if (with_rope || rw) {
     const int64_t rdense[2] = {R * kRopeDim, kRopeDim};
     const int64_t* rs = k_rope_strides ? k_rope_strides : rdense;
-    if (!aligned16(k_rope))
+    if (with_rope && !aligned16(k_rope))
       return fail(MFA_ERR_UNSUPPORTED, "%s: k_rope rows must be 16-byte aligned", what);
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; with_rope && j < 2; ++j)
       if (rs[j] < 0 || rs[j] % 8 != 0)
         return fail(MFA_ERR_UNSUPPORTED, "%s: k_rope stride %d is not a multiple of 8 elements",
                     what, j);
     mfa::PagedRopeAppendParams pr;
     memset(&pr, 0, sizeof(pr));
-    pr.src[0] = latent; pr.src[1] = k_rope;
-    pr.pool[0] = const_cast<void*>(cache->pool); pr.pool[1] = const_cast<void*>(rope->pool);
+    pr.src[0] = latent;
+    pr.pool[0] = const_cast<void*>(cache->pool);
     pr.s_sb[0] = s[0] * 2; pr.s_ss[0] = s[1] * 2;
-    pr.s_sb[1] = rs[0] * 2; pr.s_ss[1] = rs[1] * 2;
     pr.page_bytes[0] = cache->strides[0] * cv.es; pr.tok_bytes[0] = cache->strides[1] * cv.es;
-    pr.page_bytes[1] = rope->strides[0] * cv.es; pr.tok_bytes[1] = rope->strides[1] * cv.es;
-    pr.chunks[0] = (int)Lat / 8; pr.chunks[1] = kRopeDim / 8;
+    pr.chunks[0] = (int)Lat / 8;
+    if (with_rope) {  // the rope part is 16-bit beside an INT8 latent too
+      pr.src[1] = k_rope;
+      pr.pool[1] = const_cast<void*>(rope->pool);
+      pr.s_sb[1] = rs[0] * 2; pr.s_ss[1] = rs[1] * 2;
+      pr.page_bytes[1] = rope->strides[0] * 2; pr.tok_bytes[1] = rope->strides[1] * 2;
+      pr.chunks[1] = kRopeDim / 8;
+    }
     pr.pg = cv.pg;
     pr.new_lens = new_lens;
     pr.R = (int)R;
     pr.cap = (int)cv.cap;
     pr.rows_total = (int)(B * R);
+    if (rw) {
+      mfa::PagedLatentRw8AppendParams pw;
+      memset(&pw, 0, sizeof(pw));
+      pw.a = pr;
+      pw.scales = const_cast<float*>(rw->scales->scales);
+      pw.sc_page = rw->scales->page_stride;
+      return hip_status(mfa::paged_latent_append_rw8_dispatch(pw, elem_of(prec), stream),
+                        "mfa_paged_latent_append_rowwise launch");
+    }
     return hip_status(mfa::paged_rope_append_dispatch(pr, stream),
                       "mfa_paged_latent_rope_append launch");
   }
@@ -2936,6 +3017,83 @@ extern "C" mfa_status_t mfa_paged_latent_rope_append_plan(
     const mfa_paged_rope_cache_t r = plan_rope(rope, c);
     return paged_latent_append(desc, vd, nullptr, nullptr, &c, nullptr, true, vd, nullptr, &r);
   });
+}
+
+// The scales struct of a row-wise latent plan query: the given one with a null pool replaced or,
+// without one, a dense pool over the cache's pages.
+static mfa_paged_latent_scales_t plan_latent_scales(const mfa_paged_latent_scales_t* scales,
+                                                    const mfa_paged_latent_cache_t& c) {
+  mfa_paged_latent_scales_t s;
+  if (scales) {
+    s = *scales;
+  } else {
+    memset(&s, 0, sizeof(s));
+    s.page_stride = c.page_size;
+  }
+  fill_dummy(s.scales);
+  return s;
+}
+
+extern "C" mfa_status_t mfa_paged_latent_append_rowwise(
+    const mfa_paged_latent_append_descriptor_t* desc, const void* latent,
+    const int64_t* latent_strides, const void* k_rope, const int64_t* k_rope_strides,
+    const int32_t* new_lens, const mfa_paged_latent_cache_t* cache,
+    const mfa_paged_latent_scales_t* scales, const mfa_paged_rope_cache_t* rope, void* stream) {
+  const LatentRowwiseArg rw{scales};
+  return paged_latent_append(desc, latent, latent_strides, new_lens, cache, (hipStream_t)stream,
+                             k_rope || rope, k_rope, k_rope_strides, rope, &rw);
+}
+
+extern "C" mfa_status_t mfa_paged_latent_append_rowwise_plan(
+    const mfa_paged_latent_append_descriptor_t* desc, const mfa_paged_latent_cache_t* cache,
+    const mfa_paged_latent_scales_t* scales, const mfa_paged_rope_cache_t* rope,
+    int32_t with_rope, mfa_kernel_plan_t* out) {
+  if (!desc || !out || (!with_rope && rope)) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  const void* const vd = (const void*)kPlanDummy;
+  return paged_latent_plan(
+      *desc, cache, out,
+      [&](const mfa_paged_latent_cache_t& c) {
+        const mfa_paged_latent_scales_t s = plan_latent_scales(scales, c);
+        const LatentRowwiseArg rw{&s};
+        if (!with_rope)
+          return paged_latent_append(desc, vd, nullptr, nullptr, &c, nullptr, false, nullptr,
+                                     nullptr, nullptr, &rw);
+        const mfa_paged_rope_cache_t r = plan_rope(rope, c);
+        return paged_latent_append(desc, vd, nullptr, nullptr, &c, nullptr, true, vd, nullptr, &r,
+                                   &rw);
+      },
+      true);
+}
+
+extern "C" mfa_status_t mfa_paged_mla_decode_forward_rowwise(
+    const mfa_paged_mla_descriptor_t* desc, const void* query, const void* q_rope, const void* w_k,
+    const void* w_v, const mfa_paged_latent_cache_t* cache,
+    const mfa_paged_latent_scales_t* scales, const mfa_paged_rope_cache_t* rope, float* output,
+    void* logsumexp, void* stream) {
+  const LatentRowwiseArg rw{scales};
+  return paged_mla_decode(desc, query, w_k, w_v, cache, output, logsumexp, (hipStream_t)stream,
+                          q_rope || rope, q_rope, rope, &rw);
+}
+
+extern "C" mfa_status_t mfa_paged_mla_decode_rowwise_plan(
+    const mfa_paged_mla_descriptor_t* desc, const mfa_paged_latent_cache_t* cache,
+    const mfa_paged_latent_scales_t* scales, const mfa_paged_rope_cache_t* rope,
+    int32_t with_rope, mfa_kernel_plan_t* out) {
+  if (!desc || !out || (!with_rope && rope)) return fail(MFA_ERR_INVALID_ARGUMENT, "null argument");
+  const void* const vd = (const void*)kPlanDummy;
+  return paged_latent_plan(
+      *desc, cache, out,
+      [&](const mfa_paged_latent_cache_t& c) {
+        const mfa_paged_latent_scales_t s = plan_latent_scales(scales, c);
+        const LatentRowwiseArg rw{&s};
+        if (!with_rope)
+          return paged_mla_decode(desc, vd, vd, vd, &c, (float*)kPlanDummy, nullptr, nullptr,
+                                  false, nullptr, nullptr, &rw);
+        const mfa_paged_rope_cache_t r = plan_rope(rope, c);
+        return paged_mla_decode(desc, vd, vd, vd, &c, (float*)kPlanDummy, nullptr, nullptr, true,
+                                vd, &r, &rw);
+      },
+      true);
 }
 
 extern "C" mfa_status_t mfa_paged_mla_rope_prefill_forward(

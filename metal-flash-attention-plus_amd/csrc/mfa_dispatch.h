@@ -109,6 +109,10 @@ hipError_t paged_append_rowwise_dispatch(const PagedAppendRwParams& p, int elem,
 // The latent row and its 64-element rope key row to slot t of the same page, one launch
 // (mfa_paged_latent_rope_append); 16-bit rows of either type, the bits unchanged.
 hipError_t paged_rope_append_dispatch(const PagedRopeAppendParams& p, hipStream_t stream);
+// The latent row quantised to INT8 with its own amax / 127 scale, and the rope row (where there
+// is one) copied, in one launch (mfa_paged_latent_append_rw8_kernel); lat = 256 or 512.
+hipError_t paged_latent_append_rw8_dispatch(const PagedLatentRw8AppendParams& p, int elem,
+                                            hipStream_t stream);
 // FP16 Q with per-tensor INT8 / INT4 K/V (src SRC_I8 / SRC_I4) widened on load inside the
 // shared-tile loop (attention_fwd_kv8.hip); D <= 128 padded to 128, no masks.
 hipError_t fwd_kv8_dispatch(const FwdParams& p, int elem, int DP, int src, hipStream_t stream);
@@ -143,6 +147,13 @@ hipError_t mla_latent_paged_dispatch(const LatentPagedParams& p, int elem, int l
 // ... with the rope key part: mfa_mla_latent_paged_rope_kernel, then the same merge.
 hipError_t mla_latent_paged_rope_dispatch(const LatentPagedRopeParams& p, int elem, int lat,
                                           hipStream_t stream);
+// The merge of the key splits alone (mfa_mla_latent_merge_kernel, one row per workgroup), for a
+// latent kernel that lives in another file.
+hipError_t mla_latent_merge_dispatch(const LatentParams& p, int elem, int lat, hipStream_t stream);
+// The paged route over a row-wise INT8 latent pool (attention_mla_latent_rw8.hip):
+// mfa_mla_latent_paged_rw8_kernel with or without the rope key part, then that merge.
+hipError_t mla_latent_paged_rw8_dispatch(const LatentPagedRw8Params& p, bool rope, int elem,
+                                         int lat, hipStream_t stream);
 // Ragged prompt chunks over that cache: one launch of 32-row query blocks, no key split, the
 // 16-bit latent-space output in p.c.l.olat (the caller applies W_v).
 hipError_t mla_latent_prefill_dispatch(const LatentPrefillParams& p, int elem, int lat,

@@ -189,6 +189,16 @@ struct PagedRopeAppendParams {
   int32_t rows_total;          // B · R
 };
 
+// Row-wise append to an INT8 latent cache (mfa_paged_latent_append_rw8_kernel): a's latent pool
+// holds bytes (a.page_bytes[0] / a.tok_bytes[0] in bytes, a.chunks[0] the 16-byte chunks of a
+// SOURCE row, Lat / 8); each written row gets scale = amax / 127 in its slot of `scales`.  The
+// rope part is copied as in a; without one a.src[1] and a.pool[1] are null.
+struct PagedLatentRw8AppendParams {
+  PagedRopeAppendParams a;
+  float* scales;             // page p, slot t at p·sc_page + t
+  int64_t sc_page;           // floats
+};
+
 // MFMA GEMM (gemm.hip): C = A·B (+C); two (B, C) pairs share A when b[1] != nullptr.
 struct GemmParams {
   const void* a;
@@ -243,6 +253,15 @@ struct LatentPagedRopeParams {
   int64_t rope_page_bytes;   // byte stride between its pages
   int64_t rope_tok_bytes;    // ... and between the token slots of a page
   const void* q_rope;        // [B][R][64] 16-bit, R = H·S_q as in c.l
+};
+
+// ... over a row-wise INT8 latent pool (mfa_mla_latent_paged_rw8_kernel): r.c.l.lat holds bytes
+// (r.c.tok_bytes and r.c.pg.page_bytes are byte strides as ever) and key j's row is
+// E(scales[j] · q_j).  The rope part stays 16-bit; without one r.rope and r.q_rope are null.
+struct LatentPagedRw8Params {
+  LatentPagedRopeParams r;
+  const float* scales;       // page p, slot t at p·sc_page + t
+  int64_t sc_page;           // floats
 };
 
 // Ragged prompt chunks over the same cache (mfa_mla_latent_prefill_kernel): c.l.Sq is the rows

@@ -17,6 +17,9 @@
 // mfa_paged_kv_append_rowwise has a kernel of its own as well (mfa_paged_append_rowwise_kernel):
 // INT8 pools with one scale per written (row, kv head), computed from the row as it is written.
 //
+// mfa_paged_latent_append_rowwise is that quantiser on the latent row, with the rope row copied
+// by the same wave (mfa_paged_latent_append_rw8_kernel).
+//
 // Memory-bound, one launch for K and V (blockIdx.y picks the operand).  A wave owns one
 // (sequence, row) at a time: length, row count and block-table entry are uniform loads on the
 // scalar path and the position, page and both base addresses are formed once per row; the lanes
@@ -254,6 +257,83 @@ hipError_t paged_rope_append_dispatch(const PagedRopeAppendParams& p, hipStream_
   const int64_t wgs = (p.rows_total + kAppendWaves - 1) / kAppendWaves;
   return launch(mfa_paged_rope_append_kernel, dim3((unsigned)std::min<int64_t>(wgs, 32768)),
                 dim3(64 * kAppendWaves), 0, stream, p);
+}
+
+// The latent row of one new token into a row-wise INT8 latent pool
+// (mfa_paged_latent_append_rowwise): the row-wise quantiser above on one "head" of Lat elements,
+// in the rope append's skeleton (a wave per (sequence, row), position and page from uniform
+// loads).  A row of 512 (256) elements is one 16-byte load in each of 64 (32) lanes — eight
+// elements per lane in registers; the amax (fmaxf: NaNs are ignored) meets the wave's in six
+// __shfl_xor steps, every lane forms scale = amax >= 2^-64 ? amax / 127 : 1 itself, quantises its
+// eight registers, q = clamp(round_half_away(x / scale), -127, 127) with a NaN element 0, and
+// stores eight bytes; lane 0 stores the scale.  With a rope part, lanes 0..7 then copy the rope
+// row's eight 16-byte chunks, the bits unchanged.  The input is read once; no LDS, no second pass.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+template <class E>
+__global__ __launch_bounds__(64 * kAppendWaves) void mfa_paged_latent_append_rw8_kernel(
+    PagedLatentRw8AppendParams pw) {
+  const PagedRopeAppendParams& p = pw.a;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const bool live = lane < p.chunks[0];                    // Lat / 8 lanes hold the row
+  const bool rope_lane = p.src[1] != nullptr && lane < p.chunks[1];
+  for (int64_t row64 = (int64_t)blockIdx.x * kAppendWaves + wave; row64 < p.rows_total;
+       row64 += (int64_t)gridDim.x * kAppendWaves) {
+    const int row = (int)row64;
+    const int b = row / p.R, r = row - b * p.R;
+    const int len = ((append_i32_ptr)p.pg.seq_lens)[b];
+    const int n = p.new_lens ? min(max(((append_i32_ptr)p.new_lens)[b], 0), p.R) : p.R;
+    const int64_t t64 = (int64_t)len - n + r;  // any int32 length: no wrap
+    if (r >= n || t64 < 0 || t64 >= p.cap) continue;
+    const int t = (int)t64;  // < cap <= max_pages * page: the lookup stays in the table row
+    const int entry = ((append_i32_ptr)p.pg.block_table)[(int64_t)b * p.pg.max_pages +
+                                                         (t >> p.pg.lg_page)];
+    const int page = min(max(entry, 0), p.pg.num_pages - 1);
+    const int slot = t & ((1 << p.pg.lg_page) - 1);
+    u32x4 w = u32x4{0u, 0u, 0u, 0u};
+    if (live)
+      w = *(const u32x4*)((const char*)p.src[0] + b * p.s_sb[0] + r * p.s_ss[0] + 16 * lane);
+    float x[8];
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      x[k] = E::to_f32((uint16_t)(w[k >> 1] >> (16 * (k & 1))));
+      a = fmaxf(a, fabsf(x[k]));
+    }
+    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o));
+    const float scale = a >= kRowwiseFloor ? a / 127.0f : 1.0f;
+    if (live) {
+      uint32_t q[2] = {0u, 0u};
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float rq = roundf(x[k] / scale);  // half away from zero
+        const int32_t i = !(rq == rq) ? 0 : (int32_t)fminf(fmaxf(rq, -127.f), 127.f);
+        q[k >> 2] |= (uint32_t)(uint8_t)(int8_t)i << (8 * (k & 3));
+      }
+      *(u32x2*)((char*)p.pool[0] + (int64_t)page * p.page_bytes[0] +
+                (int64_t)slot * p.tok_bytes[0] + 8 * lane) = u32x2{q[0], q[1]};
+      if (lane == 0) pw.scales[(int64_t)page * pw.sc_page + slot] = scale;
+    }
+    if (rope_lane) {
+      const char* const sp = (const char*)p.src[1] + b * p.s_sb[1] + r * p.s_ss[1] + 16 * lane;
+      char* const dp = (char*)p.pool[1] + (int64_t)page * p.page_bytes[1] +
+                       (int64_t)slot * p.tok_bytes[1] + 16 * lane;
+      *(u32x4*)dp = *(const u32x4*)sp;
+    }
+  }
+}
+
+hipError_t paged_latent_append_rw8_dispatch(const PagedLatentRw8AppendParams& p, int elem,
+                                            hipStream_t stream) {
+  // mfa_paged_append_kernel's grid for one operand.
+  const int64_t wgs = (p.a.rows_total + kAppendWaves - 1) / kAppendWaves;
+  const dim3 grid((unsigned)std::min<int64_t>(wgs, 32768)), block(64 * kAppendWaves);
+  if (elem == P_FP16)
+    return launch(mfa_paged_latent_append_rw8_kernel<F16>, grid, block, 0, stream, p);
+  if (elem == P_BF16)
+    return launch(mfa_paged_latent_append_rw8_kernel<BF16>, grid, block, 0, stream, p);
+  return hipErrorNotSupported;
 }
 
 hipError_t paged_append_dispatch(const PagedAppendParams& p, int elem, bool i8, int operands,

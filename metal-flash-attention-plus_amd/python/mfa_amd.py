@@ -553,6 +553,25 @@ class PagedRopeCache(ctypes.Structure):
         return c
 
 
+class PagedLatentScales(ctypes.Structure):
+    """mfa_paged_latent_scales_t: one FP32 scale per token slot next to a PagedLatentCache whose
+    precision is INT8 (row-wise quantised latent rows)."""
+    _fields_ = [
+        ("scales", ctypes.c_void_p),
+        ("page_stride", ctypes.c_int64),
+    ]
+
+    @classmethod
+    def make(cls, page_size, scales=None, page_stride=None):
+        """Scale pool [num_pages, page_size] FP32 unless `page_stride` (floats) says otherwise.
+        The tensor may be None for a plan query."""
+        s = cls()
+        s.scales = _ptr(scales)
+        s.page_stride = int(page_size if page_stride is None else page_stride)
+        s._keep = (scales,)  # the struct holds a raw device pointer
+        return s
+
+
 class PagedMLADecodeDescriptor(ctypes.Structure):
     """mfa_paged_mla_descriptor_t: R query rows per head over a paged latent cache."""
     _fields_ = [
@@ -701,6 +720,18 @@ _sig("mfa_paged_mla_rope_prefill_forward", ctypes.c_int,
       _V, _V, _V])
 _sig("mfa_paged_mla_rope_prefill_plan", ctypes.c_int,
      [_P(PagedMLADecodeDescriptor), _P(PagedLatentCache), _P(PagedRopeCache), _P(KernelPlan)])
+_sig("mfa_paged_latent_append_rowwise", ctypes.c_int,
+     [_P(PagedLatentAppendDescriptor), _V, _P(ctypes.c_int64), _V, _P(ctypes.c_int64), _V,
+      _P(PagedLatentCache), _P(PagedLatentScales), _P(PagedRopeCache), _V])
+_sig("mfa_paged_latent_append_rowwise_plan", ctypes.c_int,
+     [_P(PagedLatentAppendDescriptor), _P(PagedLatentCache), _P(PagedLatentScales),
+      _P(PagedRopeCache), ctypes.c_int32, _P(KernelPlan)])
+_sig("mfa_paged_mla_decode_forward_rowwise", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _V, _V, _V, _V, _P(PagedLatentCache), _P(PagedLatentScales),
+      _P(PagedRopeCache), _V, _V, _V])
+_sig("mfa_paged_mla_decode_rowwise_plan", ctypes.c_int,
+     [_P(PagedMLADecodeDescriptor), _P(PagedLatentCache), _P(PagedLatentScales),
+      _P(PagedRopeCache), ctypes.c_int32, _P(KernelPlan)])
 _sig("mfa_quantize_workspace_size", ctypes.c_size_t,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32])
 _sig("mfa_quantize", ctypes.c_int,
@@ -1234,6 +1265,63 @@ def paged_mla_rope_prefill_plan(desc: PagedMLADecodeDescriptor,
     multihead_plan); without a rope view, a dense rope pool over the cache's pages.  Needs no
     GPU."""
     return _rope_plan(lib.mfa_paged_mla_rope_prefill_plan, desc, cache, rope)
+
+
+def paged_latent_append_rowwise(desc: PagedLatentAppendDescriptor, latent, cache: PagedLatentCache,
+                                scales: PagedLatentScales, k_rope=None,
+                                rope: Optional[PagedRopeCache] = None, new_lens=None,
+                                latent_strides=None, k_rope_strides=None, stream=None):
+    """mfa_paged_latent_append_rowwise: paged_latent_rope_append into an INT8 latent cache — every
+    written latent row is quantised with a scale of its own, amax / 127, stored in its slot of
+    `scales`; the rope rows (k_rope and rope given together, or neither) are copied unchanged."""
+    check(lib.mfa_paged_latent_append_rowwise(
+        ctypes.byref(desc), _ptr(latent), _strides2(latent, latent_strides), _ptr(k_rope),
+        None if k_rope is None else _strides2(k_rope, k_rope_strides), _ptr(new_lens),
+        ctypes.byref(cache), _ref(scales), _ref(rope), _stream(stream)))
+
+
+def _rowwise_latent_plan(fn, desc, cache, scales, rope, with_rope) -> list[dict]:
+    plan = KernelPlan()
+    check(fn(ctypes.byref(desc), _ref(cache), _ref(scales), _ref(rope), int(bool(with_rope)),
+             ctypes.byref(plan)))
+    return plan.as_list()
+
+
+def paged_latent_append_rowwise_plan(desc: PagedLatentAppendDescriptor,
+                                     cache: Optional[PagedLatentCache] = None,
+                                     scales: Optional[PagedLatentScales] = None,
+                                     rope: Optional[PagedRopeCache] = None,
+                                     with_rope=False) -> list[dict]:
+    """mfa_paged_latent_append_rowwise_plan: the kernel paged_latent_append_rowwise launches, with
+    a rope part (with_rope, or a rope view given) or without; missing structs are planned as dense
+    pools over an INT8 cache of 256-key pages.  Needs no GPU."""
+    return _rowwise_latent_plan(lib.mfa_paged_latent_append_rowwise_plan, desc, cache, scales,
+                                rope, with_rope or rope is not None)
+
+
+def paged_mla_decode_forward_rowwise(desc: PagedMLADecodeDescriptor, query, w_k, w_v,
+                                     cache: PagedLatentCache, scales: PagedLatentScales, output,
+                                     q_rope=None, rope: Optional[PagedRopeCache] = None,
+                                     logsumexp=None, stream=None):
+    """mfa_paged_mla_decode_forward_rowwise: paged_mla_decode_forward (q_rope and rope None) or
+    paged_mla_rope_decode_forward (both given) over an INT8 latent cache: key j's latent row is
+    scales[j] * q_j rounded once to the descriptor's 16-bit type, so the result equals the 16-bit
+    call's on a pool of those rows bit for bit.  No byte or scale of a slot at or past a
+    sequence's length is read."""
+    check(lib.mfa_paged_mla_decode_forward_rowwise(
+        ctypes.byref(desc), _ptr(query), _ptr(q_rope), _ptr(w_k), _ptr(w_v), ctypes.byref(cache),
+        _ref(scales), _ref(rope), _ptr(output), _ptr(logsumexp), _stream(stream)))
+
+
+def paged_mla_decode_rowwise_plan(desc: PagedMLADecodeDescriptor,
+                                  cache: Optional[PagedLatentCache] = None,
+                                  scales: Optional[PagedLatentScales] = None,
+                                  rope: Optional[PagedRopeCache] = None,
+                                  with_rope=False) -> list[dict]:
+    """mfa_paged_mla_decode_rowwise_plan: the kernels paged_mla_decode_forward_rowwise launches
+    (see paged_latent_append_rowwise_plan for the arguments).  Needs no GPU."""
+    return _rowwise_latent_plan(lib.mfa_paged_mla_decode_rowwise_plan, desc, cache, scales, rope,
+                                with_rope or rope is not None)
 
 
 def quantize(x, target: Precision, mode: QuantMode = QuantMode.tensorWise, rows=None, cols=None,
